@@ -12,14 +12,18 @@ density + colour MLPs, packed compositing, huber loss, backward, (RCCL all-reduc
 100th step, wherever that falls - the occupancy prune (nerf.py:175-212).
 Prints ONE JSON line (rank 0).  Inputs are synthetic (synlego.py) and resident in HBM before the timed region.
 
-Sequence: dense level-7 octree (nerf_hash.yaml:16-17) -> `--pretrain` untimed optimisation steps with the trainer's own
-adaptive ray count and pruning -> W warm-up + exactly K timed steps at `--target-samples` packed samples per step - the
-reference trainer's own batch, 2^18 (multiview_trainer.py:58): the headline `value` -> W + K steps at `--large-target-samples`
+A plain run does what the headline needs and nothing else: dense level-7 octree (nerf_hash.yaml:16-17) -> `--pretrain`
+untimed optimisation steps with the trainer's own adaptive ray count and pruning -> W warm-up + exactly K timed steps at
+`--target-samples` packed samples per step - the reference trainer's own batch, 2^18 (multiview_trainer.py:58): the headline
+`value` -> one prune timed on its own (`prune`, charged to `value` as K/100 prunes) -> `--dump-outputs DIR` if given (the timed
+loop for a few steps more, on seeded inputs: _fixed_input_steps) -> the line.
+
+`--full` runs everything else the line carries, in this order: headline -> W + K steps at `--large-target-samples`
 (2^21, 8 x the reference's) with the learning rates scaled by sqrt(batch ratio) (`large_batch_regime`: more rays per second,
 less quality per ray - `quality` holds the held-out PSNR of both regimes against rays consumed and against wall-clock,
 profiles/r06_time_to_psnr_*.txt) -> the unchanged trainer (`dropin_regime`) -> one prune timed on its own (`prune`) -> PSNR on
-held-out rays -> live rocprofv3 --pmc passes for `roofline.traffic` -> the N > 1 launch structure on one GPU
-(`dp_path_regime`) -> CPU oracle baseline.
+held-out rays -> live rocprofv3 --pmc passes for `roofline.traffic` -> `configs` -> `quality` -> the N > 1 launch structure on
+one GPU (`dp_path_regime`) -> CPU oracle baseline.
 """
 import argparse
 import json
@@ -85,6 +89,14 @@ def parse(argv=None):
     ap.add_argument("--dp-steps", type=int, default=30,
                     help="one GPU only: timed steps of the N > 1 launch structure (gradient collective on a side stream + separate "
                          "optimizer) over a one-rank RCCL group, reported as dp_path_regime; 0 skips it")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: large_batch_regime, dropin_regime, held-out PSNR, the live "
+                         "rocprofv3 --pmc passes, configs, quality, dp_path_regime, cpu_baseline (each still switchable off by its "
+                         "own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed loop for a few steps more on inputs fixed by seeds (a fresh model on "
+                         "the scene's occupancy, seeded batches) and write what it computed as DIR/<name>.npy: the losses and "
+                         "packed sample count, the decoder and its AdamW moments, a seeded sample of the tables' AdamW moments")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -614,6 +626,75 @@ def _leaf_cells(pipe):
     return int(blas.pyramid[0, blas.max_level])                          # leaf cells of the (pruned) octree
 
 
+DUMP_SAMPLE = 2 ** 20                 # table elements kept per dumped array (a fixed, seeded sample)
+DUMP_SEED = 4321
+DUMP_STEPS = 8                        # steps of the timed loop the dump runs: past AdamW's first step (bias correction, moments)
+
+
+def _fixed_input_steps(args, dev, rank, make_trainer, bank_o, bank_d, bank_rgb, common_rays):
+    """--dump-outputs: the timed loop - MultiviewTrainStep.step with the run's configuration, at the headline's packed-sample
+    target, with its one-batch look-ahead - for DUMP_STEPS steps on inputs fixed by seeds alone: a fresh model initialised like
+    the benchmark's, on the scene's occupied level-7 cells (the occupancy the pre-training prunes toward; seeded, unlike the
+    learned one), fed seeded batches of the resident ray bank.  The trained model of the timed steps cannot be that input: the
+    hash-grid backward sums its coarse levels with float atomics, and over the hundreds of steps and the prunes before the last
+    timed one two runs with the same arguments drift apart far beyond rounding (occupied cells, table values by percents).
+    -> {name: float32 / float64 array} on rank 0 (None elsewhere), all after the last of the DUMP_STEPS steps:
+       loss, samples                 what the last step returns (its forward's loss; the packed samples of its raymarch)
+       losses                        what every one of the steps returned as its loss
+       params_decoder                the decoder's weights
+       exp_avg_decoder, exp_avg_sq_decoder    the decoder's AdamW moments
+       exp_avg_grid, exp_avg_sq_grid          the hash-grid tables' AdamW moments (their gradients, accumulated), each a fixed
+                                     seeded sample of DUMP_SAMPLE elements.  The tables' own values are not written: AdamW's
+                                     first step moves an entry by +-lr whatever the size of its gradient, so an entry whose
+                                     float-atomic gradient sum lies within rounding of zero can land 2 lr apart between runs.
+    The dump's trainer keeps the whole optimizer state on every rank (sharded_optimizer=False), so rank 0 holds all of it."""
+    from wisp.core import Rays
+    import synlego
+    pipe = build_pipeline(dev, args.hidden, args.num_steps, synlego.occupied_cells(7, device=dev))
+    trainer = make_trainer(pipe, sharded_optimizer=False)
+    gen = torch.Generator(device=dev).manual_seed(DUMP_SEED + rank)
+
+    def batch(n):
+        idx = torch.randint(0, bank_o.shape[0], (n,), device=dev, generator=gen)
+        o, d, rgb = _gather_rows(idx, [bank_o, bank_d, bank_rgb])
+        return Rays(o, d, dist_min=synlego.NEAR, dist_max=synlego.FAR), rgb
+
+    probe, _ = batch(4096)
+    pipe.tracer.prev_num_samples = _probe_samples(pipe, probe, args.num_steps)
+    R = common_rays(trainer.calc_adaptive_rays(4096))
+    rays, gts = batch(R)
+    losses = []
+    for _ in range(DUMP_STEPS):
+        nrays, ngts = batch(R)
+        loss, samples = trainer.step(rays, gts, prefetch=nrays)
+        losses.append(loss)
+        rays, gts = nrays, ngts
+    _sync()
+    if rank != 0:
+        return None
+    f = trainer.flat
+    out = {"loss": np.array([float(losses[-1])], dtype=np.float64), "samples": np.array([float(samples)], dtype=np.float64),
+           "losses": np.array([float(x) for x in losses], dtype=np.float64)}
+    a, b = f.ranges["decoder"]
+    out["params_decoder"] = f.data[a:b].detach().float().cpu().numpy()
+    out["exp_avg_decoder"] = f.exp_avg[a:b].detach().float().cpu().numpy()
+    out["exp_avg_sq_decoder"] = f.exp_avg_sq[a:b].detach().float().cpu().numpy()
+    a, b = f.ranges["grid"]
+    idx = None
+    if b - a > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(b - a, DUMP_SAMPLE, replace=False))).to(f.data.device)
+    for name in ("exp_avg", "exp_avg_sq"):
+        m = getattr(f, name)[a:b]
+        out[name + "_grid"] = (m if idx is None else m[idx]).detach().float().cpu().numpy()
+    return out
+
+
+def _write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class _StdoutForTheLineOnly:
     """The contract is ONE JSON line on stdout.  Libraries write there too - RCCL prints a version banner from C stdio when a process
     group comes up, and its buffered tail is flushed at exit, i.e. AFTER a line printed from Python - so file descriptor 1 points at
@@ -682,6 +763,7 @@ def _main(argv, guard):
     if args.config != "nerf_hash":
         import bench_configs
         assert world == 1, "the secondary configs are single-GPU lines"
+        assert not args.dump_outputs, "--dump-outputs writes the nerf_hash step's outputs; the secondary configs have none"
         return bench_configs.main(args, dev, emit=guard.emit)
     if args.pmc_child:                                     # profiling child: fixed occupancy, a handful of steps, no extras
         args.occupancy, args.pretrain, args.warmup, args.steps = "analytic", 0, 2, 4
@@ -696,8 +778,11 @@ def _main(argv, guard):
     cells = _initial_cells(args, dev, true_cells)
     pipe = build_pipeline(dev, args.hidden, args.num_steps, cells)
     amp = args.precision == "bf16"
-    trainer = MultiviewTrainStep(pipe, lr=1e-3, eps=1e-16, weight_decay=1e-6, grid_lr_weight=500.0, rgb_loss_type='huber',
-                                 prune_every=100, target_sample_size=args.target_samples, max_rays=2 ** 18, enable_amp=amp)
+
+    def make_trainer(p, **kw):
+        return MultiviewTrainStep(p, lr=1e-3, eps=1e-16, weight_decay=1e-6, grid_lr_weight=500.0, rgb_loss_type='huber',
+                                  prune_every=100, target_sample_size=args.target_samples, max_rays=2 ** 18, enable_amp=amp, **kw)
+    trainer = make_trainer(pipe)
 
     # ---- ray bank resident in HBM (this rank's shard of the training rays) + ground truth
     bank_o, bank_d, bank_rgb = synlego.ray_bank(args.bank_rays, seed=1000 + rank, device=dev)
@@ -809,7 +894,7 @@ def _main(argv, guard):
 
     # ---- large_batch_regime: 8 x the reference's batch (the headline until round 5), learning rates x sqrt(batch ratio), same model
     large = None
-    if args.large_target_samples > 0:
+    if args.full and args.large_target_samples > 0:
         R_large = size_batch(args.large_target_samples)
         base_lr, trainer.lr = trainer.lr, trainer.lr * large_lr
         timing_large = {}
@@ -823,16 +908,27 @@ def _main(argv, guard):
     # ---- the unchanged-application regime: the reference trainer's own step (multiview_trainer.py:111-180 through
     # BaseTrainer.iterate, base_trainer.py:316-342) over a copy of the same model state: fp16 autocast + GradScaler, autograd over
     # the modular pipeline, torch.optim.AdamW with the reference's parameter groups, SampleRays batches, two .item() per step
-    trainer.sync_master()               # (sharded optimizer: the copy below must not start from rows that are stale on this rank)
-    with _regime("dropin_regime", dev):
-        dropin = dropin_regime(pipe, bank_o, bank_d, bank_rgb, args, world, dev) if args.dropin_steps > 0 else None
+    dropin = None
+    if args.full:
+        trainer.sync_master()           # (sharded optimizer: the copy below must not start from rows that are stale on this rank)
+        with _regime("dropin_regime", dev):
+            dropin = dropin_regime(pipe, bank_o, bank_d, bank_rgb, args, world, dev) if args.dropin_steps > 0 else None
 
     # ---- one prune, timed on its own (it falls into the timed steps only every 100th iteration)
+    trainer.sync_master()               # (sharded optimizer: the fp32 all-gather stays outside the prune's window)
     _sync()
     tp = time.perf_counter()
     trainer.prune()
     _sync()
     prune_ms = 1e3 * (time.perf_counter() - tp)
+
+    # ---- --dump-outputs: DUMP_STEPS more steps of the timed loop, outside every timed window, on inputs the same on every run
+    outputs = None
+    if args.dump_outputs:
+        with torch.random.fork_rng(devices=[dev] if dev.type == "cuda" else []):      # (the --full measurements keep their RNG)
+            outputs = _fixed_input_steps(args, dev, rank, make_trainer, bank_o, bank_d, bank_rgb, common_rays)
+        if dev.type == "cuda":
+            torch.cuda.empty_cache()
 
     # ---- per-kernel roofline from the live HIP events (algorithmic bytes: SURVEY.md 8d / DESIGN.md)
     d = getattr(trainer, "_direct", None)
@@ -868,7 +964,7 @@ def _main(argv, guard):
             bound, achieved = rate(dominant, k)
             peak, unit = peaks[bound]
             roofline = dict(bound=bound, kernel=dominant, achieved=achieved, peak=peak, unit=unit, frac=achieved / peak,
-                            traffic=None, traffic_note="not measured (--no-pmc, multi-GPU run or profiler unavailable); see profiles/",
+                            traffic=None, traffic_note="not measured (no --full, --no-pmc, multi-GPU run or profiler unavailable); see profiles/",
                             avg_launch_ms=k["avg_ms"], units_per_launch=k["avg_units"], work_per_unit=work[dominant][1],
                             levels_processed=live_levels, levels_of_the_table=NGP["num_lods"],
                             work_note="algorithmic bytes of the levels the kernels process: lod_idx = 15 zeroes the finest level's columns "
@@ -906,7 +1002,7 @@ def _main(argv, guard):
     if rank == 0:
         # quality: PSNR on held-out rays after pretrain + warm-up + both timed loops (real optimisation steps all of them)
         psnr = None
-        if args.eval_rays > 0:
+        if args.full and args.eval_rays > 0:
             with torch.no_grad(), torch.autocast(dev.type, dtype=torch.bfloat16, enabled=amp):
                 eo, ed, ergb = synlego.ray_bank(args.eval_rays, seed=7, device=dev)
                 chunks = []
@@ -938,6 +1034,7 @@ def _main(argv, guard):
             "metric": "training rays/sec, HashGrid NeRF (nerf_hash.yaml), synthetic Lego 800x800",
             "value": rays_total / amort, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * amort / args.steps, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "full": args.full,
             "timed_window": {"seconds": elapsed, "ms_per_step": 1e3 * elapsed / args.steps, "value": rays_total / elapsed,
                              "prunes_inside": prunes_in, "prunes_charged": args.steps / trainer.prune_every if trainer.prune_every > 0 else 0.0,
                              "note": "`value` = rays / (window seconds + (steps / prune_every - prunes_inside) x prune.ms)"},
@@ -969,7 +1066,7 @@ def _main(argv, guard):
         }
         if roofline and scratch:
             roofline["hashgrid_bwd_scratch"] = scratch
-        if world == 1 and roofline and not args.no_pmc:
+        if args.full and world == 1 and roofline and not args.no_pmc:
             groups = {roofline["kernel"]: PMC_KERNELS[roofline["kernel"]]}
             if "hashgrid_fwd" in roofline["all_kernels"]:
                 groups["hashgrid_fwd"] = PMC_KERNELS["hashgrid_fwd"]
@@ -988,7 +1085,7 @@ def _main(argv, guard):
                              note="bound by the L2-miss fill path: `achieved` = memory-side bytes of the L2s per launch (live FETCH_SIZE x2 + "
                                   "WRITE_SIZE; Infinity-Cache hits included) / launch time, against the 8 TB/s HBM peak (6.29 TB/s is the "
                                   "copy rate the guide measures); l2_request_gbs = L2 requests x 128 B against the L2s' 34.5 TB/s")
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             # the other BASELINE.json configurations + the reference's best published row (hidden 128), a few steps each
             import bench_configs
             out["configs"] = bench_configs.secondary_lines(args, dev)
@@ -996,15 +1093,17 @@ def _main(argv, guard):
             if args.large_target_samples > 0 and "error" not in out["configs"]["hidden128"]:
                 big = hidden128_line(args, dev, pipe, batch, args.large_target_samples)
                 out["configs"]["hidden128"]["large_batch_regime"] = big
-        if world == 1 and args.quality_budget > 0:
+        if args.full and world == 1 and args.quality_budget > 0:
             out["quality"] = quality_table(args, dev, (bank_o, bank_d, bank_rgb), amp, large_lr)
-        if world == 1 and args.dp_steps > 0 and not dist.is_initialized():
+        if args.full and world == 1 and args.dp_steps > 0 and not dist.is_initialized():
             out["dp_path_regime"] = dp_path_regime(args, dev, pipe, batch, R, out["ms_per_step"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(true_cells, args.hidden, args.num_steps)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
+    if outputs is not None:
+        _write_outputs(args.dump_outputs, outputs)
     if out is not None:
         guard.emit(json.dumps(out))
     return out

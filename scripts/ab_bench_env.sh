@@ -6,7 +6,7 @@ OUT=$1; ROUNDS=$2; shift 2
 for r in $(seq 1 $ROUNDS); do
   for e in "$@"; do
     envs=""; [ "$e" != "-" ] && envs="$e"
-    line=$(env $envs python bench.py --steps 200 --no-configs --no-cpu-baseline --no-pmc --quality-budget 0 --dp-steps 0 --dropin-steps 0 ${AB_BENCH_ARGS:---large-target-samples 0} 2>/dev/null | tail -1)
+    line=$(env $envs python bench.py --full --steps 200 --no-configs --no-cpu-baseline --no-pmc --quality-budget 0 --dp-steps 0 --dropin-steps 0 ${AB_BENCH_ARGS:---large-target-samples 0} 2>/dev/null | tail -1)
     python - "$e" "$r" "$line" >> $OUT <<'PY'
 import json, sys
 e, r, line = sys.argv[1:4]

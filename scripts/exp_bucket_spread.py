@@ -22,7 +22,7 @@ C.hashgrid_interpolate_backward = spy
 import io, contextlib
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
-    bench.main(["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-pmc", "--no-configs", "--dropin-steps", "0"])
+    bench.main(["--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-pmc", "--no-configs", "--dropin-steps", "0"])
 coords, res, bw = seen["coords"], seen["res"], seen["bw"]
 n = coords.shape[0]
 dev = coords.device

@@ -25,7 +25,7 @@ bench.dropin_regime = wrapped
 iters = os.environ.get("EXP_ITERS", "600")
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
-    bench.main(["--steps", "200", "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs", "--dropin-steps", iters])
+    bench.main(["--full", "--steps", "200", "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs", "--dropin-steps", iters])
 j = json.loads(buf.getvalue().strip().splitlines()[-1])
 n = int(iters) + 107
 print("freeze=%s: drop-in %.3f ms per iteration over %s timed iterations; collections during the %d iterations of dropin_regime (warm-up included): %s; objects tracked now: %d, frozen: %d" % (

@@ -35,7 +35,7 @@ def wrapped(*a, **k):
 bench.dropin_regime = wrapped
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
-    bench.main(["--steps", sys.argv[1], "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs"])
+    bench.main(["--full", "--steps", sys.argv[1], "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs"])
 j = json.loads(buf.getvalue().strip().splitlines()[-1])
 iters = wait[1] / 4.0 if wait[1] else 1
 clk = os.popen("rocm-smi --showclocks 2>/dev/null | grep -E 'sclk|mclk' | head -2").read().strip().replace("\n", " | ")

@@ -20,7 +20,7 @@ def wrapped(*a, **k):
 bench.dropin_regime = wrapped
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
-    bench.main(["--steps", sys.argv[1], "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs"])
+    bench.main(["--full", "--steps", sys.argv[1], "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs"])
 j = json.loads(buf.getvalue().strip().splitlines()[-1])
 print("steps %s: drop-in %.3f ms per iteration (under cProfile); own ms / cumulative ms / calls" % (sys.argv[1], j["dropin_regime"]["ms_per_step"]))
 for tt, ct, nc, name in sorted(rows, reverse=True)[:int(sys.argv[2]) if len(sys.argv) > 2 else 32]:

@@ -25,7 +25,7 @@ C._SlotFit._collect = collect
 import bench
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
-    bench.main(["--steps", "200", "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs", "--dropin-steps", "0"])
+    bench.main(["--full", "--steps", "200", "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--no-configs", "--dropin-steps", "0"])
 j = json.loads(buf.getvalue().strip().splitlines()[-1])
 print("headroom %s, a check every %d launches: %d checks, %d of them saw a full slot (%d level-checks), fullest slot / capacity at most %.2f; scratch at the end %.3f GB, step %.4f ms" % (
     os.environ.get("WISP_HG_SLOT_HEADROOM", "1.2"), every, seen["checks"], seen["overflowing_checks"], seen["levels"], seen["worst"],

@@ -18,11 +18,11 @@ if has tests; then
   timeout 300 python __graft_entry__.py smoke 2>&1 | grep -v amdgpu.ids > $OUT/smoke.log; echo "smoke exit ${PIPESTATUS[0]}" >> $OUT/smoke.log; tail -2 $OUT/smoke.log
 fi
 if has bench; then
-  timeout 1500 python bench.py 2>&1 | grep -v amdgpu.ids > $OUT/bench_default.log; tail -1 $OUT/bench_default.log | cut -c1-600
-  timeout 600 python bench.py --precision fp32 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --steps 40 2>&1 | grep -v amdgpu.ids > $OUT/bench_fp32.log; tail -1 $OUT/bench_fp32.log | cut -c1-300
+  timeout 1500 python bench.py --full 2>&1 | grep -v amdgpu.ids > $OUT/bench_default.log; tail -1 $OUT/bench_default.log | cut -c1-600
+  timeout 600 python bench.py --full --precision fp32 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --steps 40 2>&1 | grep -v amdgpu.ids > $OUT/bench_fp32.log; tail -1 $OUT/bench_fp32.log | cut -c1-300
 fi
 if has trace; then
-  (cd /tmp && rm -rf /tmp/prof && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python "$REPO/bench.py" --steps 60 --pretrain 300 --eval-rays 0 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 > "$REPO/$OUT/prof.log" 2>&1)
+  (cd /tmp && rm -rf /tmp/prof && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python "$REPO/bench.py" --full --steps 60 --pretrain 300 --eval-rays 0 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 > "$REPO/$OUT/prof.log" 2>&1)
   find /tmp/prof -name "*kernel_stats.csv" -exec cp {} $OUT/r04_bench_default_kernel_stats.csv \;
   python scripts/trace_gaps.py /tmp/prof hashgrid_fwd 100 > $OUT/r04_step_timeline_2p21.txt 2>&1; head -24 $OUT/r04_step_timeline_2p21.txt
   python scripts/trace_gaps.py /tmp/prof > $OUT/r04_step_timeline_2p18.txt 2>&1; head -8 $OUT/r04_step_timeline_2p18.txt
@@ -34,7 +34,7 @@ if has configs; then
     (cd /tmp && rm -rf /tmp/prof_$cfg && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$cfg -o p -- python "$REPO/bench.py" --config $cfg --steps 30 --pretrain 50 > /dev/null 2>&1)
     find /tmp/prof_$cfg -name "*kernel_stats.csv" -exec cp {} $OUT/r04_${cfg}_kernel_stats.csv \;
   done
-  timeout 600 python bench.py --hidden 128 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --steps 60 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r04_bench_hidden128.json
+  timeout 600 python bench.py --full --hidden 128 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --steps 60 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r04_bench_hidden128.json
 fi
 RX="hashgrid|mlp_|raymarch|composite|adamw"
 if has pmc; then

@@ -11,13 +11,13 @@ timeout 900 python -m pytest tests -m gpu -q -k "folded or off_a_16_byte or adam
 fi
 run() { # label, env...
   local label=$1; shift
-  env "$@" timeout 600 python bench.py --steps ${STEPS:-200} --no-pmc --no-configs --no-cpu-baseline --dropin-steps 0 2>&1 | grep -v amdgpu.ids | tail -1 > /tmp/b.json
+  env "$@" timeout 600 python bench.py --full --steps ${STEPS:-200} --no-pmc --no-configs --no-cpu-baseline --dropin-steps 0 2>&1 | grep -v amdgpu.ids | tail -1 > /tmp/b.json
   python - $label <<'PY'
 import json, sys
 j = json.loads(open('/tmp/b.json').read())
 r = j['roofline']
 k = r['all_kernels']
-print(sys.argv[1].ljust(6), 'ms/step %.4f' % j['ms_per_step'], 'ref-regime %.4f (no prunes %.4f)' % (j['reference_regime']['ms_per_step'], j['reference_regime']['ms_per_step_without_its_prunes']),
+print(sys.argv[1].ljust(6), 'ms/step %.4f' % j['ms_per_step'], '2^21 %.4f (window %.4f)' % (j['large_batch_regime']['ms_per_step'], j['large_batch_regime']['timed_window']['ms_per_step']),
       'psnr %.2f' % j['psnr_db'], {n: round(v['avg_ms'], 4) for n, v in k.items()}, 'bwd frac', round(k['hashgrid_bwd']['frac'], 3),
       k['hashgrid_bwd'].get('fused_optimizer', {}).get('frac_on_the_backward_bytes_alone'))
 PY

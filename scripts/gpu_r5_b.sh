@@ -19,15 +19,15 @@ echo "pytest (selection) exit $?: $(tail -1 $OUT/pytest_sel.log)"
 timeout 600 python -m pytest tests/test_gpu_1_selfcheck.py -x -q --tb=short -p no:cacheprovider -k "128 or composite or direct" > $OUT/pytest_sel2.log 2>&1
 echo "pytest (selfcheck selection) exit $?: $(tail -1 $OUT/pytest_sel2.log)"
 for w in 1 2 4; do
-  WISP_COMPOSITE_WAVES=$w timeout 600 python bench.py --steps 100 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --eval-rays 0 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/bench_cw$w.json
+  WISP_COMPOSITE_WAVES=$w timeout 600 python bench.py --full --steps 100 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --eval-rays 0 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/bench_cw$w.json
   python - $w $OUT/bench_cw$w.json <<'PY'
 import json, sys
 j = json.load(open(sys.argv[2]))
-print('composite waves', sys.argv[1], 'ms/step %.4f' % j['timed_window']['ms_per_step'], 'ref-regime %.4f (no prunes %.4f)' % (j['reference_regime']['ms_per_step'], j['reference_regime']['ms_per_step_without_its_prunes']))
+print('composite waves', sys.argv[1], 'ms/step %.4f' % j['timed_window']['ms_per_step'], '2^21 %.4f (window %.4f)' % (j['large_batch_regime']['ms_per_step'], j['large_batch_regime']['timed_window']['ms_per_step']))
 PY
 done
 for v in 1 0; do
-  WISP_WIDE_DW=$v timeout 600 python bench.py --hidden 128 --steps 60 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/bench_h128_dw$v.json
+  WISP_WIDE_DW=$v timeout 600 python bench.py --full --hidden 128 --steps 60 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/bench_h128_dw$v.json
   python - $v $OUT/bench_h128_dw$v.json <<'PY'
 import json, sys
 j = json.load(open(sys.argv[2]))

@@ -18,9 +18,9 @@ if has tests; then
   timeout 300 python __graft_entry__.py smoke 2>&1 | grep -v amdgpu.ids > $OUT/smoke.log; echo "smoke exit ${PIPESTATUS[0]}" >> $OUT/smoke.log; tail -2 $OUT/smoke.log
 fi
 if has bench; then
-  timeout 1500 python bench.py 2>&1 | grep -v amdgpu.ids > $OUT/bench_default.log; tail -1 $OUT/bench_default.log > $OUT/r06_bench_default.json; cut -c1-600 $OUT/r06_bench_default.json
+  timeout 1500 python bench.py --full 2>&1 | grep -v amdgpu.ids > $OUT/bench_default.log; tail -1 $OUT/bench_default.log > $OUT/r06_bench_default.json; cut -c1-600 $OUT/r06_bench_default.json
   ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r06_bench_driver_command.json ) 2> $OUT/driver_command_time.txt; cut -c1-300 $OUT/r06_bench_driver_command.json; tail -3 $OUT/driver_command_time.txt
-  timeout 600 python bench.py --precision fp32 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --quality-budget 0 --dp-steps 0 --steps 40 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r06_bench_fp32.json; cut -c1-300 $OUT/r06_bench_fp32.json
+  timeout 600 python bench.py --full --precision fp32 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --quality-budget 0 --dp-steps 0 --steps 40 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r06_bench_fp32.json; cut -c1-300 $OUT/r06_bench_fp32.json
 fi
 if has trace; then
   bash scripts/regime_stats.sh $OUT r06
@@ -30,7 +30,7 @@ if has configs; then
     timeout 600 python bench.py --config $cfg --steps 100 --pretrain 200 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r06_bench_$cfg.json
     cut -c1-300 $OUT/r06_bench_$cfg.json; echo
   done
-  timeout 600 python bench.py --hidden 128 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --quality-budget 0 --dp-steps 0 --steps 60 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r06_bench_hidden128.json
+  timeout 600 python bench.py --full --hidden 128 --no-cpu-baseline --no-pmc --no-configs --dropin-steps 0 --quality-budget 0 --dp-steps 0 --steps 60 2>&1 | grep -v amdgpu.ids | tail -1 > $OUT/r06_bench_hidden128.json
   cut -c1-300 $OUT/r06_bench_hidden128.json; echo
 fi
 RX="hashgrid|mlp_|raymarch|composite|adamw"

@@ -1,7 +1,7 @@
 """CPU, world_size 2, gloo: bench.py's own main() driven through its world > 1 control flow - rendezvous from
 the torch.distributed.run environment, the collective self-test and its WISP_SHARDED_OPTIM fallback (a reduce-scatter made to
 fail softly), common_rays, the barrier / max-over-ranks timing of timed_steps, all_sum,
-comm_summary, the reference regime, the prune timing, the PSNR pass and the JSON line of rank 0.  The HIP kernels cannot run
+comm_summary, the reference regime, the prune timing, the PSNR pass (--full) and the JSON line of rank 0.  The HIP kernels cannot run
 here: the per-ray work is the stand-in field of tests/test_distributed_gloo.py and the few runtime hooks bench.py exposes for
 this purpose (device, process group, synchronise, row gather, probe raymarch) are replaced; every other line of main() runs as
 the 8-GPU driver will run it."""
@@ -20,7 +20,7 @@ from test_distributed_gloo import _free_port
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench_worker(rank, world, port, out, break_reduce_scatter, precision, extra=()):
+def _bench_worker(rank, world, port, out, break_reduce_scatter, precision, extra=("--full",)):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     os.environ.pop("WISP_SHARDED_OPTIM", None)
     sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd")]
@@ -79,7 +79,7 @@ def test_bench_main_world2_gloo_strong_scaling_splits_the_global_batch():
     world = 2
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_bench_worker, args=(world, _free_port(), out, False, "fp32", ("--scaling", "strong")), nprocs=world, join=True)
+    mp.spawn(_bench_worker, args=(world, _free_port(), out, False, "fp32", ("--full", "--scaling", "strong")), nprocs=world, join=True)
     line = json.loads(dict(out)[0]["printed"][0])
     assert line["scaling"] == "strong" and line["n_gpus"] == 2
     cfg = line["config"]
@@ -88,6 +88,37 @@ def test_bench_main_world2_gloo_strong_scaling_splits_the_global_batch():
     assert line["large_batch_regime"]["rays_per_step_per_gpu"] == max(256, int(4096 * (65536 // 2) / (4096 * 12)))
     R = cfg["rays_per_step_per_gpu"]
     assert abs(line["value"] - R * 4 * 2 / (line["ms_per_step"] * 4e-3)) <= 1e-6 * line["value"]      # still the whole job's rays / s
+
+
+def test_bench_main_world2_gloo_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline alone (no large_batch_regime, drop-in regime or PSNR pass; the prune is still
+    timed, `value` is charged with it); --dump-outputs runs a few steps more of the timed loop on seeded inputs, on both ranks, and
+    rank 0 writes what they computed - losses, sample count, decoder and its AdamW moments, the tables' AdamW moments - as
+    float32 / float64 .npy files."""
+    world = 2
+    mgr = mp.Manager()
+    out = mgr.dict()
+    dump = str(tmp_path / "outputs")
+    mp.spawn(_bench_worker, args=(world, _free_port(), out, False, "bf16", ("--dump-outputs", dump)), nprocs=world, join=True)
+    res = dict(out)
+    assert len(res[0]["printed"]) == 1 and res[1]["printed"] == []
+    line = json.loads(res[0]["printed"][0])
+    assert line["full"] is False and line["steps"] == 4 and line["warmup"] == 1 and line["n_gpus"] == 2
+    assert line["large_batch_regime"] is None and line["dropin_regime"] is None and line["psnr_db"] is None
+    assert "quality" not in line and "configs" not in line and "cpu_baseline" not in line and "dp_path_regime" not in line
+    assert line["prune"]["ms"] >= 0.0 and line["comm"]["selftest"]["rccl_ranks"] == 2
+    R = line["config"]["rays_per_step_per_gpu"]
+    assert abs(line["value"] - R * 4 * 2 / (line["ms_per_step"] * 4e-3)) <= 1e-6 * line["value"]
+    import numpy as np
+    files = sorted(os.listdir(dump))
+    assert files == ["exp_avg_decoder.npy", "exp_avg_grid.npy", "exp_avg_sq_decoder.npy", "exp_avg_sq_grid.npy", "loss.npy",
+                     "losses.npy", "params_decoder.npy", "samples.npy"], files
+    arrays = {f[:-4]: np.load(os.path.join(dump, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert arrays["loss"].shape == (1,) and np.isfinite(arrays["loss"]).all() and arrays["samples"][0] > 0
+    assert arrays["losses"].shape == (8,) and arrays["losses"][-1] == arrays["loss"][0]
+    assert (arrays["exp_avg_sq_decoder"] >= 0).all() and (arrays["exp_avg_sq_grid"] >= 0).all()
+    assert all(np.isfinite(a).all() and a.size > 0 for a in arrays.values())
 
 
 STANDIN_ARGS = ["--steps", "3", "--warmup", "1", "--pretrain", "2", "--precision", "fp32", "--target-samples", "16384",

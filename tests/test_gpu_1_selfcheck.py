@@ -1391,14 +1391,14 @@ def test_bench_line_on_the_gpu_has_the_contract_fields_and_is_alone_on_stdout():
     """`python bench.py` in a short form, as a subprocess on the real device: exactly ONE line on stdout (RCCL's banner of the
     one-rank group of dp_path_regime must not reach it), and in it the contract's fields - metric / value / unit / n_gpus / steps
     / warmup / ms_per_step / scaling / dtype / config.workload, `roofline` (bound, achieved, peak, unit, frac, traffic) - plus
-    this repository's regimes: large_batch_regime with its own roofline, quality, dropin_regime, dp_path_regime."""
+    this repository's regimes (--full): large_batch_regime with its own roofline, quality, dropin_regime, dp_path_regime."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--pretrain", "30",
            "--bank-rays", "131072", "--eval-rays", "4096", "--large-target-samples", "524288", "--quality-budget", "200000",
-           "--dp-steps", "4", "--dropin-steps", "5", "--no-configs", "--no-cpu-baseline", "--no-pmc"]
+           "--dp-steps", "4", "--dropin-steps", "5", "--no-configs", "--no-cpu-baseline", "--no-pmc", "--full"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1421,3 +1421,51 @@ def test_bench_line_on_the_gpu_has_the_contract_fields_and_is_alone_on_stdout():
     dp = d["dp_path_regime"]
     assert "error" not in dp and dp["allreduce"]["ms_per_step"] > 0 and dp["sharded"]["comm"]["path"].startswith("reduce-scatter")
     assert "PROJECTION" in dp["allreduce"]["projected_n8"]["note"]
+
+
+def test_plain_bench_line_is_the_headline_alone_and_its_dumped_outputs_repeat(tmp_path):
+    """`python bench.py` without --full, as a subprocess on the real device, twice: one line, the contract's fields, none of the
+    --full regimes, at most 30 s of the run's wall time outside its warm-up and timed steps; --dump-outputs writes the timed
+    loop's outputs on seeded inputs (losses, sample count, decoder and its AdamW moments, the tables' AdamW moments; float32 /
+    float64, well under 64 MB), and the two runs write the same values: the sample count exactly, the rest within float
+    rounding carried through a few steps (the hash-grid backward sums coarse levels with float atomics)."""
+    import json
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = ["exp_avg_decoder", "exp_avg_grid", "exp_avg_sq_decoder", "exp_avg_sq_grid", "loss", "losses", "params_decoder", "samples"]
+    got = []
+    for run in range(2):
+        dump = str(tmp_path / f"outputs{run}")
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", dump]
+        t0 = time.perf_counter()
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        wall = time.perf_counter() - t0
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps", "warmup", "roofline", "prune"):
+            assert k in d, k
+        assert d["full"] is False and d["steps"] == 20 and d["warmup"] == 5 and d["dtype"] == "bf16" and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["rays_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["large_batch_regime"] is None and d["dropin_regime"] is None and d["psnr_db"] is None
+        assert not {"quality", "configs", "cpu_baseline", "dp_path_regime"} & set(d)
+        outside = wall - 25 * d["ms_per_step"] * 1e-3
+        assert outside < 30.0, f"{outside:.1f} s of a plain run outside its 25 steps"
+        files = sorted(os.listdir(dump))
+        assert files == [n + ".npy" for n in names], files
+        arrays = {n: np.load(os.path.join(dump, n + ".npy")) for n in names}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+        assert 0.0 < arrays["loss"][0] < 1.0 and 2 ** 16 < arrays["samples"][0] < 2 ** 20 and arrays["losses"][-1] == arrays["loss"][0]
+        assert arrays["exp_avg_grid"].size == 2 ** 20 and np.abs(arrays["exp_avg_grid"]).max() > 0
+        got.append(arrays)
+    a, b = got
+    assert a["samples"][0] == b["samples"][0]
+    for n in names:
+        x, y = a[n].astype(np.float64), b[n].astype(np.float64)
+        scale = float(np.abs(x).max())
+        err = float(np.abs(x - y).max())
+        assert err <= 1e-4 * scale, (n, err, scale)
