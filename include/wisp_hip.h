@@ -685,6 +685,30 @@ int wisp_nerf_step_run(void* step, int slot, const float* gts, const float* next
  * most 512 steps: later steps go untimed until it is read). */
 int wisp_nerf_step_read_timing(void* step, int max_steps, float* ms, int64_t* units, int* num_steps);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh -> signed distance, brute force over every (point, triangle) pair  (replaces wisp._C.external.mesh_to_sdf_cuda and
+ * mesh_to_sdf_triangle_cuda: wisp/csrc/external/mesh_to_sdf.cpp:23-43, kernels wisp/csrc/external/mesh2sdf_kernel.cu:334-583,
+ * :585-840, :844-970, host code :1230-1330).  Rule and float roundings: DESIGN.md section 7.
+ *
+ *  points        f64 [n, 3]
+ *  mesh          f64 [f, 3, 3]   triangle corners (the reference's V[F])
+ *  sdf           f64 [n]         |sdf| = sqrtf of the float-rounded min distsq; negative iff all 13 stabbing directions hit
+ *                                the mesh on both sides of the point
+ *  out           f64 [2n]        (triangle variant) sdf, then the index of the nearest triangle as a double: the lowest index
+ *                                whose float distsq is the minimum, -1 if every triangle is degenerate
+ *  triangle_ranges       0 = chosen from n so that small point sets still fill the GPU; > 0 forces that many ranges per launch
+ *  max_pairs_per_launch  0 = 2^34; each launch evaluates at most this many pairs (at least one triangle per launch)
+ *  workspace     wisp_mesh_sdf_workspace_bytes(n, f) bytes of device scratch (triangle records + per-point combine words)
+ * The result is bitwise the same for every triangle_ranges / max_pairs_per_launch (ranges combine with atomic min / or).
+ * n >= 1, f >= 1.
+ */
+int wisp_mesh_to_sdf(const double* points, int64_t n, const double* mesh, int64_t f, int triangle_ranges,
+                     int64_t max_pairs_per_launch, double* sdf, void* workspace, int64_t workspace_bytes, wisp_stream_t stream);
+int wisp_mesh_to_sdf_triangle(const double* points, int64_t n, const double* mesh, int64_t f, int triangle_ranges,
+                              int64_t max_pairs_per_launch, double* out, void* workspace, int64_t workspace_bytes,
+                              wisp_stream_t stream);
+int64_t wisp_mesh_sdf_workspace_bytes(int64_t n, int64_t f);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,10 +118,13 @@ SIGNATURES = {
     "wisp_nerf_step_count": [c_vp, c_i32, c_vp, c_vp, c_i64, c_u64, c_vp],
     "wisp_nerf_step_run": [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp],
     "wisp_nerf_step_read_timing": [c_vp, c_i32, c_vp, c_vp, c_vp],
+    "wisp_mesh_to_sdf": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "wisp_mesh_to_sdf_triangle": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "wisp_mesh_sdf_workspace_bytes": [c_i64, c_i64],
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
-_RESTYPES = {"wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
+_RESTYPES = {"wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
              "wisp_last_error": ctypes.c_char_p, "wisp_host_reader_create": c_vp, "wisp_host_reader_destroy": None,
              "wisp_nerf_step_config_bytes": c_i64, "wisp_nerf_step_workspace_bytes": c_i64, "wisp_nerf_step_create": c_vp,
              "wisp_nerf_step_destroy": None}
@@ -1450,6 +1453,29 @@ def gather_rows(index, tensors, out=None):
     return outs
 
 
+def mesh_to_sdf(points, mesh, with_triangle=False, triangle_ranges=0, max_pairs_per_launch=0):
+    """Signed distance of every point to a triangle mesh (csrc/mesh_sdf.hip, rule: DESIGN.md section 7).  points f64 [N,3] and
+    mesh f64 [F,3,3] on the GPU -> f64 [N] (or f64 [2N]: distances, then the nearest triangle's index as a double).
+    triangle_ranges / max_pairs_per_launch force the split of the work (0 = the library's choice); no split changes a bit."""
+    points, mesh = _need(points, name="points"), _need(mesh, name="mesh")
+    if points.dtype != torch.float64 or mesh.dtype != torch.float64:
+        raise RuntimeError(f"mesh_to_sdf: points and mesh must be float64, got {points.dtype} / {mesh.dtype}")
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise RuntimeError(f"mesh_to_sdf: points must be [N>=1, 3], got {tuple(points.shape)}")
+    if mesh.ndim != 3 or tuple(mesh.shape[1:]) != (3, 3) or mesh.shape[0] < 1:
+        raise RuntimeError(f"mesh_to_sdf: mesh must be [F>=1, 3, 3], got {tuple(mesh.shape)}")
+    if points.device != mesh.device:
+        raise RuntimeError(f"mesh_to_sdf: points on {points.device}, mesh on {mesh.device}")
+    n, f = points.shape[0], mesh.shape[0]
+    ws = torch.empty(lib.wisp_mesh_sdf_workspace_bytes(n, f), dtype=torch.uint8, device=points.device)
+    out = torch.empty(2 * n if with_triangle else n, dtype=torch.float64, device=points.device)
+    entry = lib.wisp_mesh_to_sdf_triangle if with_triangle else lib.wisp_mesh_to_sdf
+    with torch.cuda.device(points.device):
+        _check(entry(_p(points), n, _p(mesh), f, int(triangle_ranges), int(max_pairs_per_launch), _p(out), _p(ws), ws.numel(),
+                     _stream()), "mesh_to_sdf")
+    return out
+
+
 ADAMW_MAX_GROUPS = 4            # misc.hip
 
 
@@ -1748,3 +1774,17 @@ ops = _Namespace("wisp._C.ops",
                  hashgrid_interpolate_backward_cuda=_ref_hashgrid_interpolate_backward_cuda,
                  uniform_sample_cuda=_ref_uniform_sample_cuda)
 render = _Namespace("wisp._C.render", find_depth_bound_cuda=_ref_find_depth_bound_cuda)
+
+
+def _ref_mesh_to_sdf_cuda(points, mesh):
+    """mesh_to_sdf.cpp:23-31 -> [sdf f64 [N]]."""
+    return [mesh_to_sdf(points, mesh)]
+
+
+def _ref_mesh_to_sdf_triangle_cuda(points, mesh):
+    """mesh_to_sdf.cpp:33-43 -> [f64 [2N]]: signed distances, then nearest-triangle indices stored as doubles."""
+    return [mesh_to_sdf(points, mesh, with_triangle=True)]
+
+
+external = _Namespace("wisp._C.external", mesh_to_sdf_cuda=_ref_mesh_to_sdf_cuda,
+                      mesh_to_sdf_triangle_cuda=_ref_mesh_to_sdf_triangle_cuda)

@@ -1,4 +1,4 @@
-"""Mesh helpers behind OctreeAS.from_mesh (wisp/accelstructs/octree_as.py:65-106): OBJ geometry loading, sphere / aabb
+"""Mesh helpers behind OctreeAS.from_mesh and the SDF datasets (wisp/accelstructs/octree_as.py:65-106): OBJ geometry loading, sphere / aabb
 normalisation and area-weighted surface sampling - the subset of wisp/ops/mesh the occupancy build uses
 (load_obj.py:52, normalize.py:11, per_face_normals.py:11, area_weighted_distribution.py:12, random_face.py:13,
 sample_surface.py:13).  Construction-time torch code on whatever device the vertices live on; nothing here is on the
@@ -127,3 +127,6 @@ def barycentric_coordinates(points: torch.Tensor, A: torch.Tensor, B: torch.Tens
     out[..., 2] = torch.clip((d00 * d21 - d01 * d20) / denom, 0.0, 1.0)
     out[..., 0] = torch.clip(1.0 - (out[..., 1] + out[..., 2]), 0.0, 1.0)
     return out
+
+
+from .compute_sdf import compute_sdf, closest_point, closest_point_on_triangle     # noqa: E402

@@ -3,7 +3,8 @@ as API).  NOTHING in this package calls them: the 'voxel' march computes the sam
 (wisp_raymarch_voxel_emit), bit for bit (tests/test_gpu_0_parity.py::test_raymarch_voxel_and_uniform_bit_exact).  They exist so
 that user code importing `wisp.ops.spc.sample_from_depth_intervals / expand_pack_boundary` keeps working, and the CPU suite holds
 them to `torch.equal` with the reference's functions (same random draw, same float operations in the same order) - which pins
-the arithmetic: (k + u) * (1 / N), then entry + (exit - entry) * that, in fp32, one rounding per operation."""
+the arithmetic: (k + u) * (1 / N), then entry + (exit - entry) * that, in fp32, one rounding per operation.
+sample_spc (sampling.py:12-32) draws the 'rand' samples of OctreeSampledSDFDataset."""
 import torch
 
 
@@ -23,3 +24,13 @@ def expand_pack_boundary(pack_boundary, num_samples):
     first = pack_boundary.bool().reshape(-1, 1)
     rest = first.new_zeros(first.shape[0], num_samples - 1)
     return torch.cat([first, rest], dim=1).reshape(-1).int()
+
+
+def sample_spc(corners, level, num_samples):
+    """`num_samples` uniform draws inside each voxel of `level` whose integer corner is a row of `corners` ([M, 3+]), as
+    [M * num_samples, 3] coordinates in [-1, 1] (wisp/ops/spc/sampling.py:12-32).  One [M, num_samples, 3] fp32 draw from the
+    default generator on the corners' device, the reference's draw: the same seed gives the same samples."""
+    u = torch.rand(corners.shape[0], num_samples, 3, device=corners.device)
+    cell = (corners[..., None, :3] + u).reshape(-1, 3)
+    cell /= 2.0 ** level
+    return cell * 2.0 - 1.0
