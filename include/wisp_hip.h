@@ -37,7 +37,8 @@ const char* wisp_last_error(void);
  * passes, raytrace nugget cache, optimizer kinds, per-ray view codes, corner query, decoded codebook rows; 3 = round 3: per-level
  * slot scales of the hash-grid backward; 4 = round 4: workspace + row counts of the order-free trilinear / codebook backward.
  * Entry points that are only ADDED - wisp_spc_query_chain, wisp_composite_loss, wisp_codebook_trilinear_multi_bwd,
- * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_* - do not bump it). */
+ * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample -
+ * do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -708,6 +709,36 @@ int wisp_mesh_to_sdf_triangle(const double* points, int64_t n, const double* mes
                               int64_t max_pairs_per_launch, double* out, void* workspace, int64_t workspace_bytes,
                               wisp_stream_t stream);
 int64_t wisp_mesh_sdf_workspace_bytes(int64_t n, int64_t f);
+
+/* ------------------------------------------------------------------------------------------------
+ * Multiview image bank -> rays, colours and masks of chosen pixels  (replaces the resident per-ray tensors of
+ * NeRFSyntheticDataset._collect_data_entries, wisp/datasets/formats/nerf_standard_dataset.py:405-441 - rays generated once per
+ * view with generate_pinhole_rays and kept, colours blended against the background once and kept - and the index_select launches
+ * of SampleRays over them, wisp/datasets/transforms/ray_sampler.py:25-35).  A ray is a pure function of (camera, pixel): one
+ * launch makes, for each of num_rays pixel indices, what those tensors held at that index.
+ *
+ *  images        u8  [num_views, height, width, 4]   the files' 8-bit RGBA, full size whatever `mip` (device, 4-byte aligned)
+ *  cameras       f32 [num_views, 16]  per view: view rotation R[9] (row major, world -> camera), view translation t[3],
+ *                                     4 floats of padding (device, 16-byte aligned); read in per-ray-view mode only
+ *  camera_host   f32 [16]             the record of view `view_index` (HOST pointer); read in one-view mode only
+ *  mip           0..5: the image the pixel indices address is (height >> mip) x (width >> mip); a pixel's colour is the mean of
+ *                its 2^mip x 2^mip block of stored texels - every texel converted first (u8 / 255.0f), the converted texels summed
+ *                in row-major order over the block, times 1 / 4^mip - and is blended after that.  height and width must be
+ *                multiples of 2^mip.
+ *  has_alpha     != 0: rgb = clamp(c * a + (1 - a) * bg, 0, 1) with separately rounded multiplies and add, mask = a > 0.5
+ *                (:437-439);  0: rgb = c, mask = 1 (:435)
+ *  pix           i64 [num_rays]  row * (width >> mip) + col; a negative index counts from the end (as wisp_gather_rows)
+ *  view          i64 [num_rays] or NULL: the view of every ray; NULL = all rays belong to view_index
+ *  x0, y0        principal point, pixels from the centre of the mip-sized image;  tan_half_fov_x / _y = (size / 2) / focal
+ *  bg            f32 [3] (HOST pointer)
+ *  origins, dirs f32 [num_rays, 3]: bit for bit wisp_generate_rays at the pixel centre (col + 0.5, row + 0.5)
+ *  rgb           f32 [num_rays, 3];  mask u8 [num_rays] (0 / 1)
+ * Any of origins / dirs / rgb / mask may be NULL and is then not computed.  Pixel and view indices are trusted (no range
+ * check on the device), like the index of wisp_gather_rows. */
+int wisp_multiview_sample(const uint8_t* images, const float* cameras, const float* camera_host, int64_t num_views, int height,
+                          int width, int mip, int has_alpha, const int64_t* pix, const int64_t* view, int64_t view_index,
+                          int64_t num_rays, float x0, float y0, float tan_half_fov_x, float tan_half_fov_y, const float* bg,
+                          float* origins, float* dirs, float* rgb, uint8_t* mask, wisp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
 // reductions (deterministic, no atomics), and background blending + the scatter to per-ray buffers are
 // fused into the same kernel.
 #include "wisp_common.h"
+#include "raygen_dev.h"
 
 // Wave-wide inclusive scan / sum on the VALU (DPP), no LDS traffic: Hillis-Steele inside each 16-lane row (row_shr 1, 2, 4, 8),
 // then the row totals travel with row_bcast:15 (into rows 1 and 3) and row_bcast:31 (into rows 2 and 3).  Lanes without a
@@ -401,45 +402,19 @@ extern "C" int wisp_sphere_trace_step(int64_t num_packs, const float* nug_o, con
 // generate_pinhole_rays / generate_ortho_rays (wisp/ops/raygen/raygen.py:40-119) for one camera: pixel coordinates ->
 // principal-point shift -> NDC -> camera-space ray -> world space (inverse of the view transform: R^T (p - t)) ->
 // normalised direction.  Every step is a separately rounded fp32 operation, in the reference's order.
-struct RayCam {
-    float x0, y0, width, height;      // principal point offset (pixels from the image centre), image size
-    float sx, sy;                     // pinhole: tan(fov_x / 2), tan(fov_y / 2); ortho: fov_distance * aspect, fov_distance
-    float r[9];                       // view rotation R (row major), world -> camera
-    float t[3];                       // view translation
-};
-
+// The per-pixel arithmetic lives in raygen_dev.h (wisp_camera_ray): wisp_multiview_sample (dataset.hip) makes the same rays.
 template <bool ORTHO>
 __global__ void __launch_bounds__(256)
 raygen_kernel(const float* __restrict__ pixel_x, const float* __restrict__ pixel_y, int64_t n, RayCam cam,
               float* __restrict__ origins, float* __restrict__ dirs) {
-#pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float px = pixel_x[i], py = pixel_y[i];
-    if (!ORTHO) { px = px - cam.x0; py = py + cam.y0; }                  // raygen.py:66-67
-    px = 2.0f * (px / cam.width) - 1.0f;                                  // _to_ndc_coords, :34-37
-    py = 2.0f * (py / cam.height) - 1.0f;
-    float o[3], d[3];
-    if (ORTHO) {                                                          // :100-107
-        o[0] = px * cam.sx; o[1] = -(py * cam.sy); o[2] = 0.0f;
-        d[0] = 0.0f; d[1] = 0.0f; d[2] = -1.0f;
-    } else {                                                              // :72-77
-        o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f;
-        d[0] = px * cam.sx; d[1] = -py * cam.sy; d[2] = -1.0f;
-    }
-    // inv_transform_rays: origin' = R^T (o - t), dir' = R^T d  (sums accumulated left to right)
-    const float q[3] = {o[0] - cam.t[0], o[1] - cam.t[1], o[2] - cam.t[2]};
-    float ow[3], dw[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        ow[c] = (cam.r[0 + c] * q[0] + cam.r[3 + c] * q[1]) + cam.r[6 + c] * q[2];
-        dw[c] = (cam.r[0 + c] * d[0] + cam.r[3 + c] * d[1]) + cam.r[6 + c] * d[2];
-    }
-    const float nrm = sqrtf((dw[0] * dw[0] + dw[1] * dw[1]) + dw[2] * dw[2]);        // torch.linalg.norm
+    float ow[3], dn[3];
+    wisp_camera_ray<ORTHO>(pixel_x[i], pixel_y[i], cam, ow, dn);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         origins[i * 3 + c] = ow[c];
-        dirs[i * 3 + c] = dw[c] / nrm;
+        dirs[i * 3 + c] = dn[c];
     }
 }
 

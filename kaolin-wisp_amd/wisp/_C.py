@@ -121,6 +121,8 @@ SIGNATURES = {
     "wisp_mesh_to_sdf": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
     "wisp_mesh_to_sdf_triangle": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
     "wisp_mesh_sdf_workspace_bytes": [c_i64, c_i64],
+    "wisp_multiview_sample": [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32,
+                              c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
@@ -1451,6 +1453,48 @@ def gather_rows(index, tensors, out=None):
     w_p = (ctypes.c_int * n)(*widths)
     _check(lib.wisp_gather_rows(_p(index), index.shape[0], rows, n, src_p, w_p, dst_p, _stream()), "gather_rows")
     return outs
+
+
+def multiview_sample(images, pix, view=None, view_index=0, cameras=None, camera_host=None, mip=0, has_alpha=True, x0=0.0, y0=0.0,
+                     tan_x=1.0, tan_y=1.0, bg=(0.0, 0.0, 0.0), want=("origins", "dirs", "rgb", "mask")):
+    """Rays, colours and masks of the pixels `pix` (i64 [n], row * w + col of the mip-sized image) of a u8 [V, H, W, 4] image bank
+    (csrc/dataset.hip) - one launch.  view: i64 [n] (per-ray views; needs `cameras`, f32 [V, 16] on the device) or None = every
+    ray belongs to `view_index` (needs `camera_host`, 16 floats: that view's record).  -> dict of the outputs named in `want`:
+    origins / dirs / rgb f32 [n, 3], mask bool [n, 1]."""
+    images = _need(images, torch.uint8, "images")
+    if images.ndim != 4 or images.shape[3] != 4:
+        raise RuntimeError(f"multiview_sample: images must be u8 [V, H, W, 4], got {tuple(images.shape)}")
+    V, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    pix = _need(pix, torch.int64, "pix").reshape(-1)
+    n, dev = pix.shape[0], images.device
+    if pix.device != dev:
+        raise RuntimeError(f"multiview_sample: images on {dev}, pix on {pix.device}")
+    rays = "origins" in want or "dirs" in want
+    cam_arr = cam_ptr = None
+    if view is not None:
+        view = _need(view, torch.int64, "view").reshape(-1)
+        if view.shape[0] != n or view.device != dev:
+            raise RuntimeError("multiview_sample: view must hold one index per pixel index, on the images' device")
+        if rays:
+            cameras = _need(cameras, torch.float32, "cameras")
+            if tuple(cameras.shape) != (V, 16) or cameras.device != dev:
+                raise RuntimeError(f"multiview_sample: cameras must be f32 [{V}, 16] on {dev}, got {tuple(cameras.shape)}")
+    elif rays:
+        cam_arr, cam_ptr = _host_f32(camera_host)
+        if cam_arr.size != 16:
+            raise RuntimeError("multiview_sample: camera_host must hold the 16 floats of one camera record")
+    bg_arr, bg_ptr = _host_f32(bg)
+    assert bg_arr.size == 3
+    out = {}
+    for name in ("origins", "dirs", "rgb"):
+        out[name] = torch.empty(n, 3, dtype=torch.float32, device=dev) if name in want else None
+    out["mask"] = torch.empty(n, 1, dtype=torch.bool, device=dev) if "mask" in want else None
+    f32 = lambda v: float(np.float32(v))
+    _check(lib.wisp_multiview_sample(_p(images), _p(cameras) if view is not None and rays else None, cam_ptr, V, H, W, int(mip),
+                                     int(bool(has_alpha)), _p(pix), _p(view), int(view_index), n, f32(x0), f32(y0), f32(tan_x),
+                                     f32(tan_y), bg_ptr, _p(out["origins"]), _p(out["dirs"]), _p(out["rgb"]), _p(out["mask"]),
+                                     _stream()), "multiview_sample")
+    return {k: v for k, v in out.items() if v is not None}
 
 
 def mesh_to_sdf(points, mesh, with_triangle=False, triangle_ranges=0, max_pairs_per_launch=0):

@@ -10,3 +10,6 @@ def psnr(rgb, gts):
     assert (rgb.shape[-1] == 3) and (gts.shape[-1] == 3)
     mse = torch.mean((rgb[..., :3] - gts[..., :3]) ** 2).item()
     return 10 * np.log10(1.0 / mse)
+
+
+from .io import load_rgb, load_u8, save_u8, read_png, write_png          # noqa: E402

@@ -123,3 +123,51 @@ class LookAtCamera:
     def tan_half_fov(self, axis='horizontal'):
         t = float(np.tan(np.float64(self.fov) / 2.0))
         return t if str(axis).lower().endswith('horizontal') else t * (float(self.height) / float(self.width))
+
+
+def blender_coords():
+    """Basis of Blender's world (z up) expressed in this package's (y up, docs/pages/conventions.md): the argument
+    `camera.change_coordinate_system` takes for NeRF-synthetic data (nerf_standard_dataset.py:423)."""
+    return torch.tensor([[1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, -1.0, 0.0]])
+
+
+class PinholeCamera:
+    """A single pinhole camera given by its world -> camera view matrix and focal lengths in pixels - what
+    `Camera.from_args(view_matrix=, focal_x=, focal_y=, width=, height=, near=, far=, x0=, y0=)` builds in the reference
+    (nerf_standard_dataset.py:413-422) - with the attribute surface the ray generators read.  focal_x / focal_y stay Python
+    floats (doubles); they are rounded to fp32 only where tan_half_fov reaches a kernel."""
+
+    def __init__(self, view_matrix, focal_x, focal_y, width, height, near=1e-2, far=1e2, x0=0.0, y0=0.0, device=None):
+        m = torch.as_tensor(view_matrix, dtype=torch.float32).detach().cpu().reshape(4, 4).clone()
+        self._view = m
+        self.focal_x, self.focal_y = float(focal_x), float(focal_y)
+        self.width, self.height = int(width), int(height)
+        self.near, self.far = float(near), float(far)
+        self.x0, self.y0 = float(x0), float(y0)
+        self.fov_distance = 1.0
+        self.device = device
+
+    @classmethod
+    def from_args(cls, view_matrix, focal_x, focal_y, width, height, near=1e-2, far=1e2, x0=0.0, y0=0.0, dtype=None, device=None):
+        return cls(view_matrix, focal_x, focal_y, width, height, near=near, far=far, x0=x0, y0=y0, device=device)
+
+    def view_matrix(self):
+        return self._view[None]
+
+    def tan_half_fov(self, axis='horizontal'):
+        if str(axis).lower().endswith('horizontal'):
+            return (self.width / 2) / self.focal_x
+        return (self.height / 2) / self.focal_y
+
+    def change_coordinate_system(self, basis):
+        """Re-express the world in another basis: R_view <- R_view @ basis^T, translation unchanged - the camera sees the same
+        picture, and a world point p of the old frame is `basis @ p` in the new one."""
+        b = torch.as_tensor(basis, dtype=torch.float32).detach().cpu().reshape(3, 3)
+        self._view[:3, :3] = self._view[:3, :3] @ b.T
+        return self
+
+    def to(self, device=None, *args, **kwargs):
+        """The camera itself is host data (it reaches kernels by value); `to` only records where its rays are to be made."""
+        out = PinholeCamera(self._view, self.focal_x, self.focal_y, self.width, self.height, self.near, self.far, self.x0, self.y0,
+                            device=device if isinstance(device, (str, torch.device)) else self.device)
+        return out
