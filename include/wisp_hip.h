@@ -740,6 +740,59 @@ int wisp_multiview_sample(const uint8_t* images, const float* cameras, const flo
                           int64_t num_rays, float x0, float y0, float tan_half_fov_x, float tan_half_fov_y, const float* bg,
                           float* origins, float* dirs, float* rgb, uint8_t* mask, wisp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Single image, 8-bit RGB -> coordinates and colours of chosen pixels  (replaces the resident tensors of ImageDataset,
+ * wisp/datasets/image_dataset.py:48-59 - the image divided by 255 and kept, the [H*W, 2] coordinate grid, the [H*W, 3] pixel
+ * view: 32 bytes per pixel on the host - and the per-step CPU gather + copy of :68-69).
+ *
+ *  image         u8  [height, width, 3]  (device)
+ *  pix           i64 [n]   row * width + col, 64-bit throughout; a negative index counts from the end (as wisp_gather_rows)
+ *  coords        f32 [n, 2]   (x, y) of normalized_grid(height, width, use_aspect=False), wisp/ops/geometric.py:85-98:
+ *                             x = linspace(-1, 1, width)[col], y = linspace(1, -1, height)[row], torch's fp32 linspace bit for
+ *                             bit: step = fl32((end - start) / (steps - 1)); element i is fmaf(step, i, start) for
+ *                             i < steps / 2 and fmaf(-step, steps - 1 - i, end) otherwise; steps == 1 gives start.  The fused
+ *                             multiply-add is explicit and the compiler's own contraction is off around it.
+ *  rgb           f32 [n, 3]   float(u8) / 255.0f - an IEEE division, equal to the host's `image / 255.0` rounded to fp32 for
+ *                             all 256 values (a multiplication by the reciprocal is not)
+ * coords or rgb may be NULL and is then not computed.  height, width < 2^24.  n == 0 is a no-op.  Indices are trusted. */
+int wisp_image_sample(const uint8_t* image, int height, int width, const int64_t* pix, int64_t n, float* coords, float* rgb,
+                      wisp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * ImageNeuralField.rgb of a contiguous pixel range, one launch  (replaces the validation render of
+ * wisp/trainers/image_trainer.py:112-119: nef.rgb over 1 M-coordinate chunks = hashgrid lookup, cat, two GEMMs, sigmoid, and the
+ * float ground truth of :127 it is compared against).  Output i belongs to pixel first + i of a height x width image.
+ *
+ * Per pixel, in this order, all in fp32:
+ *   1. coordinates as wisp_image_sample forms them - or, when `coords` is not NULL, coords[i] as given;
+ *   2. the 2-D lookup of levels 0 .. active_lods - 1 with wisp_hashgrid_interpolate_fwd's level arithmetic (the same device
+ *      function) and its blend, `acc += table[idx_j] * coef_j` over the four corners in index order; the columns of the other
+ *      levels are zero (HashGrid.interpolate's 'cat' rule);
+ *   3. the embedding [x, y, sin(x), sin(y), sin(2x), sin(2y), sin(4x), sin(4y), cos(same six)] (sinf / cosf, not the fast forms);
+ *   4. h_j = relu(b1_j + sum_k in_k W1_jk), inputs in the order [32 feature columns, 14 embedding values], one fused multiply-add
+ *      per term, k ascending;
+ *   5. o_c = b2_c + sum_j h_j W2_cj, fused multiply-adds, j ascending;
+ *   6. colour = 1 / (1 + expf(-o)).
+ *
+ *  coords        f32 [n, 2] or NULL
+ *  codebook      f32 [rows, 2]; first_idx i64 [num_lods + 1] (device); resolutions i32 [num_lods] (HOST); num_lods <= 16
+ *  weights       f32, 64-byte aligned, hp = hidden_padded (a multiple of 32, <= 128; padded units have zero weights and bias):
+ *                [46][hp] the first layer transposed - rows 2 l, 2 l + 1 = level l (zero rows for l >= num_lods), rows 32..45 the
+ *                embedding - then b1 [hp], W2 [3][hp], b2 [3]
+ *  gts           u8 [height, width, 3] or NULL: the ground truth, row first + i (read only for err_partials)
+ *  out_f32       f32 [n, 3] or NULL
+ *  out_u8        u8  [n, 3] or NULL: (uint8)(fl(colour * 255.0f)), truncating - the reference's (img * 255).byte()
+ *  err_partials  f64 [wisp_image_field_render_partials of n] or NULL: per workgroup, the sum over its pixels and channels of
+ *                fl(d * d), d = fl(colour - float(gts) / 255.0f) in fp32, added up in double in a fixed order.  The caller sums
+ *                the partials (in float64).
+ * Any subset of the three outputs.  No atomics: two launches write identical bytes, and an output row does not depend on how
+ * [0, height * width) is cut into ranges. */
+int wisp_image_field_render(const float* coords, int64_t first, int64_t n, int height, int width, const float* codebook,
+                            const int64_t* first_idx, const int32_t* resolutions, int num_lods, int active_lods,
+                            int codebook_bitwidth, const float* weights, int hidden_padded, const uint8_t* gts, float* out_f32,
+                            uint8_t* out_u8, double* err_partials, wisp_stream_t stream);
+int64_t wisp_image_field_render_partials(int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,10 +123,14 @@ SIGNATURES = {
     "wisp_mesh_sdf_workspace_bytes": [c_i64, c_i64],
     "wisp_multiview_sample": [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "wisp_image_sample": [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "wisp_image_field_render": [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                c_vp, c_vp],
+    "wisp_image_field_render_partials": [c_i64],
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
-_RESTYPES = {"wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
+_RESTYPES = {"wisp_image_field_render_partials": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
              "wisp_last_error": ctypes.c_char_p, "wisp_host_reader_create": c_vp, "wisp_host_reader_destroy": None,
              "wisp_nerf_step_config_bytes": c_i64, "wisp_nerf_step_workspace_bytes": c_i64, "wisp_nerf_step_create": c_vp,
              "wisp_nerf_step_destroy": None}
@@ -1495,6 +1499,83 @@ def multiview_sample(images, pix, view=None, view_index=0, cameras=None, camera_
                                      f32(tan_y), bg_ptr, _p(out["origins"]), _p(out["dirs"]), _p(out["rgb"]), _p(out["mask"]),
                                      _stream()), "multiview_sample")
     return {k: v for k, v in out.items() if v is not None}
+
+
+def image_sample(image, pix, want=("coords", "rgb"), size=None):
+    """Coordinates and colours of the pixels `pix` (i64 [n], row * w + col) of a u8 [H, W, 3] image on the GPU
+    (csrc/image_field.hip) - one launch.  -> dict of the outputs named in `want`: coords f32 [n, 2] (normalized_grid's values),
+    rgb f32 [n, 3] (u8 / 255).  image=None with size=(H, W): the coordinates of an H x W grid alone."""
+    pix = _need(pix, torch.int64, "pix").reshape(-1)
+    if image is None:
+        if size is None or "rgb" in want:
+            raise RuntimeError("image_sample: without an image, give size=(H, W) and ask for coords alone")
+        H, W = int(size[0]), int(size[1])
+    else:
+        image = _need(image, torch.uint8, "image")
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RuntimeError(f"image_sample: image must be u8 [H, W, 3], got {tuple(image.shape)}")
+        if pix.device != image.device:
+            raise RuntimeError(f"image_sample: image on {image.device}, pix on {pix.device}")
+        H, W = int(image.shape[0]), int(image.shape[1])
+    n = pix.shape[0]
+    coords = torch.empty(n, 2, dtype=torch.float32, device=pix.device) if "coords" in want else None
+    rgb = torch.empty(n, 3, dtype=torch.float32, device=pix.device) if "rgb" in want else None
+    _check(lib.wisp_image_sample(_p(image), H, W, _p(pix), n, _p(coords), _p(rgb), _stream()), "image_sample")
+    return {k: v for k, v in (("coords", coords), ("rgb", rgb)) if v is not None}
+
+
+IMAGE_FIELD_INPUTS = 46            # csrc/image_field.hip: 16 levels x 2 features + the 14 embedding values
+IMAGE_FIELD_MAX_HIDDEN = 128
+
+
+def image_field_pack_weights(w1, b1, w2, b2, num_lods):
+    """The decoder of an ImageNeuralField in wisp_image_field_render's layout (include/wisp_hip.h): first layer transposed with
+    the rows of absent levels and the columns of padded hidden units zero, then b1, W2, b2 - one fp32 buffer."""
+    hidden, width = w1.shape
+    feat = 2 * num_lods
+    assert width == feat + 14 and hidden <= IMAGE_FIELD_MAX_HIDDEN and tuple(w2.shape) == (3, hidden)
+    hp = -(-hidden // 32) * 32
+    buf = torch.zeros(IMAGE_FIELD_INPUTS * hp + hp + 3 * hp + 16, dtype=torch.float32, device=w1.device)
+    w1t = buf[:IMAGE_FIELD_INPUTS * hp].view(IMAGE_FIELD_INPUTS, hp)
+    w1t[:feat, :hidden] = w1.detach()[:, :feat].t()
+    w1t[32:, :hidden] = w1.detach()[:, feat:].t()
+    o = IMAGE_FIELD_INPUTS * hp
+    buf[o:o + hidden] = b1.detach()
+    buf[o + hp:o + 4 * hp].view(3, hp)[:, :hidden] = w2.detach()
+    buf[o + 4 * hp:o + 4 * hp + 3] = b2.detach()
+    return buf, hp
+
+
+def image_field_render(h, w, first, n, codebook, first_idx, resolutions, codebook_bitwidth, active_lods, packed, hp, coords=None,
+                       gts_u8=None, want_f32=True, want_u8=False, want_err=False):
+    """wisp_image_field_render: ImageNeuralField.rgb of pixels [first, first + n) of an h x w image (or of `coords` f32 [n, 2]) in
+    one launch.  -> (f32 [n, 3] or None, u8 [n, 3] or None, f64 per-workgroup squared-error partials or None)."""
+    codebook = _need(codebook, torch.float32, "codebook")
+    first_idx = _need(first_idx, torch.int64, "codebook_first_idx")
+    packed = _need(packed, torch.float32, "packed weights")
+    key, _arr, res_ptr = _host_res(resolutions)
+    L = len(key)
+    if codebook.ndim != 2 or codebook.shape[1] != 2 or not 1 <= L <= 16:
+        raise RuntimeError("image_field_render: needs a [rows, 2] fp32 codebook of at most 16 levels")
+    _check_first_idx(first_idx, L, codebook.shape[0])
+    if packed.numel() < IMAGE_FIELD_INPUTS * hp + 4 * hp + 3:
+        raise RuntimeError("image_field_render: packed weights are shorter than the layout for this hidden width")
+    dev = codebook.device
+    if coords is not None:
+        coords = _need(coords, torch.float32, "coords")
+        if tuple(coords.shape) != (n, 2):
+            raise RuntimeError(f"image_field_render: coords must be [{n}, 2], got {tuple(coords.shape)}")
+    if want_err:
+        gts_u8 = _need(gts_u8, torch.uint8, "gts_u8")
+        if gts_u8.device != dev or gts_u8.numel() < (first + n) * 3:
+            raise RuntimeError("image_field_render: the ground truth does not cover the pixel range")
+    out_f32 = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_f32 else None
+    out_u8 = torch.empty(n, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    part = torch.empty(int(lib.wisp_image_field_render_partials(n)), dtype=torch.float64, device=dev) if want_err else None
+    _check(lib.wisp_image_field_render(_p(coords), int(first), int(n), int(h), int(w), _p(codebook), _p(first_idx), res_ptr, L,
+                                       int(active_lods), int(codebook_bitwidth), _p(packed), int(hp), _p(gts_u8) if want_err else None,
+                                       _p(out_f32), _p(out_u8), _p(part), _stream()), "image_field_render")
+    return out_f32, out_u8, part
 
 
 def mesh_to_sdf(points, mesh, with_triangle=False, triangle_ranges=0, max_pairs_per_launch=0):

@@ -1,5 +1,5 @@
 """Geometric helpers (wisp/ops/geometric.py): the depth-bound search of the SDF tracer (:15-22) and the sphere samplers the
-radiance field's prune draws its view directions from (:25-62)."""
+radiance field's prune draws its view directions from (:25-62), and the pixel-coordinate grid of the image application (:65-99)."""
 import numpy as np
 import torch
 
@@ -29,3 +29,18 @@ def sample_fib_sphere(n):
     polar = np.arccos(1 - 2 * k / n)
     azimuth = 2. * np.pi * k / ((1 + 5 ** 0.5) / 2)
     return np.array([np.cos(azimuth) * np.sin(polar), np.sin(azimuth) * np.sin(polar), np.cos(polar)]).transpose()
+
+
+def normalized_grid(height, width, jitter=False, device='cuda', use_aspect=True):
+    """grid[row, col] -> (x, y) of a normalized window, [height, width, 2] (wisp/ops/geometric.py:65-99): x runs -1 .. 1 along the
+    width, y runs 1 .. -1 down the height; `jitter` moves every line by up to half a pixel (x drawn before y), `use_aspect`
+    stretches the longer side by the aspect ratio."""
+    lines = {'x': torch.linspace(-1, 1, steps=width, device=device), 'y': torch.linspace(1, -1, steps=height, device=device)}
+    if jitter:
+        for axis, count in (('x', width), ('y', height)):
+            lines[axis] += (2.0 * torch.rand(count, device=device) - 1.0) * (1. / count)
+    if use_aspect and width != height:
+        longer, ratio = ('x', width / height) if width > height else ('y', height / width)
+        lines[longer] = lines[longer] * ratio
+    # every row repeats the x line, every column the y line
+    return torch.stack([lines['x'][None, :].expand(height, width), lines['y'][:, None].expand(height, width)], dim=-1)
