@@ -37,8 +37,8 @@ const char* wisp_last_error(void);
  * passes, raytrace nugget cache, optimizer kinds, per-ray view codes, corner query, decoded codebook rows; 3 = round 3: per-level
  * slot scales of the hash-grid backward; 4 = round 4: workspace + row counts of the order-free trilinear / codebook backward.
  * Entry points that are only ADDED - wisp_spc_query_chain, wisp_composite_loss, wisp_codebook_trilinear_multi_bwd,
- * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample -
- * do not bump it). */
+ * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
+ * wisp_mesh_closest_tex, wisp_mesh_sample_tex - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -709,6 +709,61 @@ int wisp_mesh_to_sdf_triangle(const double* points, int64_t n, const double* mes
                               int64_t max_pairs_per_launch, double* out, void* workspace, int64_t workspace_bytes,
                               wisp_stream_t stream);
 int64_t wisp_mesh_sdf_workspace_bytes(int64_t n, int64_t f);
+
+/* ------------------------------------------------------------------------------------------------
+ * Surface colour of a textured mesh  (replaces the torch chain of wisp/ops/mesh/closest_tex.py:43-64 behind the nearest-triangle
+ * search: closest_point_on_triangle, closest_point.py:17-107, with [N,3,3] fp64 temporaries; barycentric_coordinates.py:31-45;
+ * the UV gather and weighted sum, closest_tex.py:48-60; sample_tex.py:27-56 - one F.grid_sample per material with two host
+ * read-backs, TM.max() and mask.sum(), per material).  One launch, one thread per point.
+ *
+ * Texture bank: `texels` f32 [num_texels, 3] holds the first three channels of every diffuse map, row-major (top row first), one
+ * map after another; `materials` is one record per material id (device memory, 8-byte aligned): */
+typedef struct wisp_tex_material {
+    int64_t offset;          /* first texel of the map in `texels` (in texels, not floats) */
+    int32_t height, width;   /* of the map; either may be 1 */
+    float kd[3];             /* the material's diffuse colour (0, 0, 0 when the file gives none) */
+    int32_t has_map;         /* 0: the colour is kd;  != 0: the colour is looked up in the map */
+} wisp_tex_material;
+/*  points        f64 [n, 3]
+ *  mesh          f64 [f, 3, 3]   triangle corners (the reference's V[F]), f >= 1
+ *  tidx          f64 [n] (tidx_is_i64 == 0: the second half of wisp_mesh_to_sdf_triangle's output, used where it lies) or i64 [n]:
+ *                the triangle of every point; the kernel does not search
+ *  texv          f32 [tv, 2]     texture vertices (may be NULL when tv == 0)
+ *  texf          i64 [f, 4]      per triangle: three indices into texv and the material id
+ *  hit           f64 [n, 3]      closest point of the triangle to the point
+ *  rgb           f32 [n, 3]
+ * Per point, every operation rounded on its own (no fused multiply-add), sums of three products as (p0 + p1) + p2:
+ *   1. a, b, c = the triangle's corners, ab = b - a, ac = c - a; d1 = ab.(p - a), d2 = ac.(p - a), d3 = ab.(p - b),
+ *      d4 = ac.(p - b), d5 = ab.(p - c), d6 = ac.(p - c); va = d3 d6 - d5 d4, vb = d5 d2 - d1 d6, vc = d1 d4 - d3 d2, in fp64.  The
+ *      first rule that applies gives the hit (wisp.ops.mesh.closest_point_on_triangle's order: vertices, then edges, then face):
+ *        d1 <= 0 and d2 <= 0: a;   d3 >= 0 and d4 <= d3: b;   vc <= 0, d1 >= 0, d3 <= 0: a + (d1 / (d1 - d3)) ab;
+ *        d6 >= 0 and d5 <= d6: c;  vb <= 0, d2 >= 0, d6 <= 0: a + (d2 / (d2 - d6)) ac;
+ *        va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) (c - b);
+ *        otherwise, with inv = 1 / ((va + vb) + vc): (a + ab (vb inv)) + ac (vc inv).
+ *   2. r = hit - a; d00 = ab.ab, d01 = ab.ac, d11 = ac.ac, d20 = r.ab, d21 = r.ac, denom = d00 d11 - d01 d01, in fp64;
+ *      L1 = fl32(clip((d11 d20 - d01 d21) / denom, 0, 1)), L2 = fl32(clip((d00 d21 - d01 d20) / denom, 0, 1)), then in fp32
+ *      L0 = clip(1 - (L1 + L2), 0, 1): the rounding points of the reference, which stores into an fp32 tensor.
+ *      DELIBERATE DIFFERENCE: the dot products are formed in fp64 from the fp64 corners.  The reference forms the ones of the edge
+ *      vectors in fp32 when V is fp32 (and mixes them with the fp64 ones of the hit); on well-shaped triangles this moves the
+ *      colour by a few 1e-6.
+ *   3. (u, v) = (texv[k0] L0 + texv[k1] L1) + texv[k2] L2 in fp32, k = texf[t][0..2].
+ *   4. x = 2u - 1, y = -(2v - 1).  A material without a map gives kd bit for bit (steps 2 and 3 are skipped for it).  Otherwise
+ *      F.grid_sample(bilinear, padding_mode='reflection', align_corners=True): the source coordinates ix, iy come from the same
+ *      device function as wisp_triplane_fwd's (unnormalise, reflect into [0, size-1], clip; a size of 1 gives 0); with
+ *      x0 = floor(ix), y0 = floor(iy) the colour is t[y0][x0] wx0 wy0 + t[y0][x0+1] wx1 wy0 + t[y0+1][x0] wx0 wy1 +
+ *      t[y0+1][x0+1] wx1 wy1, summed left to right, wx1 = ix - x0, wx0 = (x0 + 1) - ix (wy alike); a corner outside the map
+ *      (its weight is 0) is left out.
+ *   5. The colour is zero for a material id < 0, an id >= num_materials, a tidx < 0 (or >= f), a texture-vertex index outside
+ *      [0, tv) on a mapped material, and a record that does not lie inside the bank.  Without a triangle the hit is taken on
+ *      triangle 0, as wisp.ops.mesh.closest_point does.
+ * n == 0 is a no-op. */
+int wisp_mesh_closest_tex(const double* points, int64_t n, const double* mesh, int64_t f, const void* tidx, int tidx_is_i64,
+                          const float* texv, int64_t tv, const int64_t* texf, const float* texels, int64_t num_texels,
+                          const wisp_tex_material* materials, int num_materials, double* hit, float* rgb, wisp_stream_t stream);
+/* Step 4 (and the zero rule of step 5) alone, behind wisp.ops.mesh.sample_tex (sample_tex.py:12-58):
+ *  uv f32 [n, 2], material i64 [n] -> rgb f32 [n, 3]. */
+int wisp_mesh_sample_tex(const float* uv, const int64_t* material, int64_t n, const float* texels, int64_t num_texels,
+                         const wisp_tex_material* materials, int num_materials, float* rgb, wisp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multiview image bank -> rays, colours and masks of chosen pixels  (replaces the resident per-ray tensors of

@@ -11,6 +11,7 @@
 // without materialising a half copy of the feature tensor: features and the result are rounded through fp16 in
 // registers.
 #include "wisp_common.h"
+#include "grid_sample_dev.h"
 
 static __device__ __forceinline__ void trilinear_coeffs(const float* __restrict__ c, const int16_t* __restrict__ pt,
                                                         int level, float (&w)[8]) {
@@ -359,18 +360,7 @@ extern "C" int wisp_codebook_decode_rows(const float* logits, const float* dicti
 #define TRI_MAX_LODS 16
 struct TriPlanes { const float* fm[TRI_MAX_LODS * 3]; float* grad[TRI_MAX_LODS * 3]; int32_t size[TRI_MAX_LODS]; };
 
-// grid_sample's coordinate pipeline for align_corners=True + reflection padding: unnormalise, reflect into [0, size-1], clip
-static __device__ __forceinline__ float tri_source_index(float g, int size) {
-    float x = (g + 1.0f) * 0.5f * (float)(size - 1);
-    const float span = (float)(size - 1);
-    if (span <= 0.0f) return 0.0f;
-    x = fabsf(x);
-    const float flips = floorf(x / span);
-    const float extra = x - flips * span;                 // fmod(x, span)
-    x = (((int)flips) & 1) ? span - extra : extra;
-    return fminf(fmaxf(x, 0.0f), span);
-}
-
+// grid_sample's coordinate pipeline (unnormalise, reflect into [0, size-1], clip): wisp_reflect_source_index, grid_sample_dev.h
 template <bool BWD>
 __global__ void __launch_bounds__(256)
 triplane_kernel(const float* __restrict__ coords, int64_t n, TriPlanes tp, int num_lods, int fdim, int sum,
@@ -386,7 +376,7 @@ triplane_kernel(const float* __restrict__ coords, int64_t n, TriPlanes tp, int n
             for (int p = 0; p < 3; ++p) {
                 const float gx = c[p == 0 ? 1 : 0];       // grid[..., 0] -> width:  x-plane y, y-plane x, z-plane x
                 const float gy = c[p == 2 ? 1 : 2];       // grid[..., 1] -> height: x-plane z, y-plane z, z-plane y
-                const float ix = tri_source_index(gx, R), iy = tri_source_index(gy, R);
+                const float ix = wisp_reflect_source_index(gx, R), iy = wisp_reflect_source_index(gy, R);
                 const float fx = floorf(ix), fy = floorf(iy);
                 const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
                 const float tx = ix - fx, ty = iy - fy;

@@ -121,6 +121,8 @@ SIGNATURES = {
     "wisp_mesh_to_sdf": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
     "wisp_mesh_to_sdf_triangle": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
     "wisp_mesh_sdf_workspace_bytes": [c_i64, c_i64],
+    "wisp_mesh_closest_tex": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp],
+    "wisp_mesh_sample_tex": [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp],
     "wisp_multiview_sample": [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_image_sample": [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp],
@@ -1599,6 +1601,65 @@ def mesh_to_sdf(points, mesh, with_triangle=False, triangle_ranges=0, max_pairs_
         _check(entry(_p(points), n, _p(mesh), f, int(triangle_ranges), int(max_pairs_per_launch), _p(out), _p(ws), ws.numel(),
                      _stream()), "mesh_to_sdf")
     return out
+
+
+class TexMaterial(ctypes.Structure):
+    """include/wisp_hip.h: wisp_tex_material, field for field (32 bytes)."""
+    _fields_ = [("offset", c_i64), ("height", c_i32), ("width", c_i32), ("kd", c_f32 * 3), ("has_map", c_i32)]
+
+
+def _tex_bank_args(texels, records, what):
+    """(texels pointer, texel count, records pointer, record count) of a texture bank: texels f32 [T,3], records u8 [M*32]."""
+    texels, records = _need(texels, torch.float32, "texels"), _need(records, torch.uint8, "materials")
+    if texels.ndim != 2 or texels.shape[1] != 3 or records.numel() % ctypes.sizeof(TexMaterial):
+        raise RuntimeError(f"{what}: the bank needs texels [T,3] and whole material records, got {tuple(texels.shape)} / {records.numel()} bytes")
+    if texels.device != records.device:
+        raise RuntimeError(f"{what}: texels on {texels.device}, material records on {records.device}")
+    return texels, records, (_p(texels) if texels.numel() else None, texels.shape[0],
+                             _p(records) if records.numel() else None, records.numel() // ctypes.sizeof(TexMaterial))
+
+
+def mesh_closest_tex(points, mesh, tidx, texv, texf, texels, records):
+    """wisp_mesh_closest_tex (csrc/mesh_tex.hip): points f64 [N,3], mesh f64 [F,3,3], tidx f64 / i64 [N], texv f32 [TV,2], texf i64
+    [F,4] and a texture bank, all on one GPU -> (hit f64 [N,3], rgb f32 [N,3])."""
+    points, mesh, tidx = _need(points, name="points"), _need(mesh, name="mesh"), _need(tidx, name="tidx")
+    texv, texf = _need(texv, torch.float32, "texv"), _need(texf, torch.int64, "texf")
+    if points.dtype != torch.float64 or mesh.dtype != torch.float64:
+        raise RuntimeError(f"mesh_closest_tex: points and mesh must be float64, got {points.dtype} / {mesh.dtype}")
+    if tidx.dtype not in (torch.float64, torch.int64):
+        raise RuntimeError(f"mesh_closest_tex: tidx must be float64 or int64, got {tidx.dtype}")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"mesh_closest_tex: points must be [N, 3], got {tuple(points.shape)}")
+    if mesh.ndim != 3 or tuple(mesh.shape[1:]) != (3, 3) or mesh.shape[0] < 1:
+        raise RuntimeError(f"mesh_closest_tex: mesh must be [F>=1, 3, 3], got {tuple(mesh.shape)}")
+    n, f = points.shape[0], mesh.shape[0]
+    if tuple(tidx.shape) != (n,) or tuple(texf.shape) != (f, 4) or texv.ndim != 2 or texv.shape[1] != 2:
+        raise RuntimeError(f"mesh_closest_tex: need tidx [{n}], texf [{f}, 4], texv [TV, 2]; got {tuple(tidx.shape)}, "
+                           f"{tuple(texf.shape)}, {tuple(texv.shape)}")
+    texels, records, bank = _tex_bank_args(texels, records, "mesh_closest_tex")
+    if len({t.device for t in (points, mesh, tidx, texv, texf, texels)}) != 1:
+        raise RuntimeError("mesh_closest_tex: all tensors must be on the same device")
+    hit = torch.empty(n, 3, dtype=torch.float64, device=points.device)
+    rgb = torch.empty(n, 3, dtype=torch.float32, device=points.device)
+    with torch.cuda.device(points.device):
+        _check(lib.wisp_mesh_closest_tex(_p(points), n, _p(mesh), f, _p(tidx), int(tidx.dtype == torch.int64),
+                                         _p(texv) if texv.numel() else None, texv.shape[0], _p(texf), *bank, _p(hit), _p(rgb),
+                                         _stream()), "mesh_closest_tex")
+    return hit, rgb
+
+
+def mesh_sample_tex(uv, material, texels, records):
+    """wisp_mesh_sample_tex: uv f32 [N,2], material i64 [N] and a texture bank on one GPU -> rgb f32 [N,3]."""
+    uv, material = _need(uv, torch.float32, "uv"), _need(material, torch.int64, "material")
+    if uv.ndim != 2 or uv.shape[1] != 2 or tuple(material.shape) != (uv.shape[0],):
+        raise RuntimeError(f"mesh_sample_tex: need uv [N, 2] and material [N], got {tuple(uv.shape)} / {tuple(material.shape)}")
+    texels, records, bank = _tex_bank_args(texels, records, "mesh_sample_tex")
+    if len({t.device for t in (uv, material, texels)}) != 1:
+        raise RuntimeError("mesh_sample_tex: all tensors must be on the same device")
+    rgb = torch.empty(uv.shape[0], 3, dtype=torch.float32, device=uv.device)
+    with torch.cuda.device(uv.device):
+        _check(lib.wisp_mesh_sample_tex(_p(uv), _p(material), uv.shape[0], *bank, _p(rgb), _stream()), "mesh_sample_tex")
+    return rgb
 
 
 ADAMW_MAX_GROUPS = 4            # misc.hip

@@ -48,16 +48,24 @@ class OctreeAS(BaseAS):
                   num_samples_on_mesh: int = 100000000) -> OctreeAS:
         """Occupancy from samples over the faces of an OBJ mesh (octree_as.py:65-106): load, sphere-normalise, sample
         `num_samples_on_mesh` surface points (+ a half-cell jittered copy), quantise to `level`.  Sampling-based, hence not
-        deterministic and not guaranteed hole-free - exactly the reference's caveat.  `sample_tex` (texture / material
-        loading, documented as unused) is not provided."""
+        deterministic and not guaranteed hole-free - exactly the reference's caveat.  `sample_tex`: also read texture
+        coordinates and materials into extent['texv' | 'texf' | 'mats'] (:86-105), and keep the device texture bank built from
+        them in extent['tex_bank']; a mesh without materials raises NotImplementedError (the reference asserts "No materials
+        detected" once it samples)."""
         from wisp.ops import mesh as mesh_ops
         if sample_tex:
-            raise NotImplementedError("OctreeAS.from_mesh(sample_tex=True): textures / materials are not read by this backend")
-        vertices, faces = mesh_ops.load_obj(mesh_path)
+            vertices, faces, texv, texf, mats = mesh_ops.load_obj(mesh_path, load_materials=True)
+            if not mats:
+                raise NotImplementedError(f"OctreeAS.from_mesh(sample_tex=True): {mesh_path} defines no materials")
+        else:
+            vertices, faces = mesh_ops.load_obj(mesh_path)
         vertices, faces = mesh_ops.normalize(vertices, faces, 'sphere')
         accel_struct = cls(wisp_spc_ops.mesh_to_octree(vertices, faces, level, num_samples_on_mesh))
         accel_struct.extent['vertices'] = vertices
         accel_struct.extent['faces'] = faces
+        if sample_tex:
+            accel_struct.extent['texv'], accel_struct.extent['texf'], accel_struct.extent['mats'] = texv, texf, mats
+            accel_struct.extent['tex_bank'] = mesh_ops.TextureBank(mats)
         return accel_struct
 
     @classmethod

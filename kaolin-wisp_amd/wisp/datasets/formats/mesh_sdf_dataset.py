@@ -4,7 +4,10 @@ their signed distances (wisp.ops.mesh.compute_sdf, the HIP kernels of csrc/mesh_
 Differences from the reference:
   * the samples stay on the device and `get_batch(indices)` reads a whole batch with one indexed load (the trainer's loader uses
     it); the reference copies everything to the host;
-  * `sample_tex=True` raises NotImplementedError: textures are not read anywhere in this package."""
+  * with `sample_tex=True` the colours come from wisp.ops.mesh.closest_tex (one HIP launch behind the nearest-triangle search,
+    csrc/mesh_tex.hip) and the texture bank is built once, not per resample(); `sdf` stays [M,1] there too (the reference's
+    textured branch leaves [M], which broadcasts to [B,B] against the field's [B,1] in SDFTrainer.step) and is bitwise what
+    compute_sdf gives; a mesh without materials raises NotImplementedError (the reference asserts "No materials detected")."""
 import logging as log
 import os
 from typing import Callable, List, Optional
@@ -38,10 +41,8 @@ class MeshSampledSDFDataset(SDFDataset):
         self.get_normals = get_normals
         self.sample_tex = sample_tex
         self.mode_norm = mode_norm
-        self.verts = self.faces = self.texv = self.texf = self.mats = None
+        self.verts = self.faces = self.texv = self.texf = self.mats = self.tex_bank = None
         self.validate(mesh_path)
-        if sample_tex:
-            raise NotImplementedError("MeshSampledSDFDataset(sample_tex=True): textures are not read by this backend")
         self.data = None
         self.load()
 
@@ -59,10 +60,19 @@ class MeshSampledSDFDataset(SDFDataset):
         return torch.device("cuda", torch.cuda.current_device()) if self.verts is None else self.verts.device
 
     def load_singleprocess(self) -> None:
-        verts, faces = mesh_ops.load_obj(self.dataset_path)
+        texv = texf = None
+        if self.sample_tex:                                # parsed and checked on the host, before anything touches a device
+            verts, faces, texv, texf, self.mats = mesh_ops.load_obj(self.dataset_path, load_materials=True)
+            if not self.mats:
+                raise NotImplementedError(f"MeshSampledSDFDataset(sample_tex=True): {self.dataset_path} defines no materials")
+            self.tex_bank = mesh_ops.TextureBank(self.mats)
+        else:
+            verts, faces = mesh_ops.load_obj(self.dataset_path)
         verts, faces = mesh_ops.normalize(verts, faces, self.mode_norm)
         dev = torch.device("cuda", torch.cuda.current_device())
         self.verts, self.faces = verts.to(dev), faces.to(dev)
+        if self.sample_tex:
+            self.texv, self.texf = texv.to(dev), texf.to(dev)
         self.resample()
 
     @classmethod
@@ -82,14 +92,19 @@ class MeshSampledSDFDataset(SDFDataset):
         return self[indices]
 
     def resample(self) -> None:
-        """A new working set: coords [M,3] f32, sdf [M,1] f64 (compute_sdf), normals [M,3] with `get_normals`."""
+        """A new working set: coords [M,3] f32, sdf [M,1] f64 (compute_sdf), normals [M,3] with `get_normals`, rgb [M,3] f32
+        with `sample_tex`."""
         log.info("Resampling mesh for new sdf samples...")
         nrm = None
         if self.get_normals:
             pts, nrm = mesh_ops.sample_surface(self.verts, self.faces, self.num_samples * len(self.sample_mode))
         else:
             pts = mesh_ops.point_sample(self.verts, self.faces, self.sample_mode, self.num_samples)
-        data = dict(coords=pts, sdf=mesh_ops.compute_sdf(self.verts, self.faces, pts))
+        if self.sample_tex:                                # one search gives the distance and the triangle of the colour
+            rgb, _, d = mesh_ops.closest_tex(self.verts, self.faces, self.texv, self.texf, self.tex_bank, pts)
+            data = dict(coords=pts, sdf=d[..., None], rgb=rgb)
+        else:
+            data = dict(coords=pts, sdf=mesh_ops.compute_sdf(self.verts, self.faces, pts))
         if nrm is not None:
             data['normals'] = nrm
         self.data = data

@@ -5,7 +5,11 @@ the HIP kernels of csrc/mesh_sdf.hip); resample() subsamples the pool.
 Differences from the reference:
   * the pool and the working set stay on the device and `get_batch(indices)` reads a whole batch with one indexed load (the
     trainer's loader uses it); the reference copies everything to the host;
-  * `sample_tex=True` raises NotImplementedError: textures are not read anywhere in this package."""
+  * with `sample_tex=True` the colours come from wisp.ops.mesh.closest_tex (one HIP launch behind the nearest-triangle search,
+    csrc/mesh_tex.hip) over the texture bank OctreeAS.from_mesh(sample_tex=True) keeps in `extent`; `sdf` stays [M,1] there too
+    (the reference's textured branch leaves [M], which broadcasts to [B,B] against the field's [B,1] in SDFTrainer.step) and is
+    bitwise what compute_sdf gives; a BLAS without materials raises NotImplementedError (the reference asserts "No materials
+    detected")."""
 import logging as log
 from typing import Callable, List, Optional
 
@@ -38,8 +42,9 @@ class OctreeSampledSDFDataset(SDFDataset):
         self.sample_tex = sample_tex
         self.samples_per_voxel = samples_per_voxel
         self.validate()
-        if sample_tex:
-            raise NotImplementedError("OctreeSampledSDFDataset(sample_tex=True): textures are not read by this backend")
+        if sample_tex and not (self.blas.extent.get('mats') and 'texv' in self.blas.extent and 'texf' in self.blas.extent):
+            raise NotImplementedError("OctreeSampledSDFDataset(sample_tex=True): the acceleration structure holds no materials "
+                                      "(build it with OctreeAS.from_mesh(..., sample_tex=True) from a mesh that has some)")
         self.data_pool = None
         self.data = None
         self.load()
@@ -81,6 +86,12 @@ class OctreeSampledSDFDataset(SDFDataset):
         # Reference quirk, kept (octree_sdf_dataset.py:129): the narrow-band filter queries level 0, whose one cell is the whole
         # cube, so it only drops the points outside [-1, 1]^3.
         pts = pts[self.blas.query(pts, 0).pidx > -1]
+        if self.sample_tex:                                # one search gives the distance and the triangle of the colour
+            ext = blas.extent
+            if 'tex_bank' not in ext:
+                ext['tex_bank'] = mesh_ops.TextureBank(ext['mats'])
+            rgb, _, d = mesh_ops.closest_tex(vertices, faces, ext['texv'], ext['texf'], ext['tex_bank'], pts)
+            return dict(coords=pts, sdf=d[..., None], rgb=rgb)
         d = mesh_ops.compute_sdf(vertices, faces, pts)
         assert d.shape[0] == pts.shape[0]
         return dict(coords=pts, sdf=d)

@@ -2,17 +2,19 @@
 normalisation and area-weighted surface sampling - the subset of wisp/ops/mesh the occupancy build uses
 (load_obj.py:52, normalize.py:11, per_face_normals.py:11, area_weighted_distribution.py:12, random_face.py:13,
 sample_surface.py:13).  Construction-time torch code on whatever device the vertices live on; nothing here is on the
-per-step path.  Materials / textures (tinyobjloader in the reference, a feature its own docstring calls unused) are not
-read."""
+per-step path.  Texture coordinates and diffuse materials are read by load_obj(load_materials=True) (obj.py, a hand-written
+parser where the reference uses tinyobjloader); surface colours come from closest_tex / sample_tex (texture.py, one HIP launch
+behind the nearest-triangle search)."""
 import torch
 
 
 def load_obj(fname: str, load_materials: bool = False):
     """Vertices float32 [V,3] and triangle indices int64 [F,3] of a Wavefront OBJ (polygons are fan-triangulated, negative
-    indices are relative to the vertices read so far, as the format defines)."""
+    indices are relative to the vertices read so far, as the format defines).  With `load_materials`: (vertices, faces, texv
+    f32 [TV,2], texf i64 [F,4], mats), see obj.load_obj_with_materials (load_obj.py:85-115)."""
     if load_materials:
-        raise NotImplementedError("load_obj(load_materials=True): textures / materials are not read by this backend "
-                                  "(OctreeAS.from_mesh(sample_tex=True) is documented as unused in the reference)")
+        from .obj import load_obj_with_materials
+        return load_obj_with_materials(fname)
     verts, faces = [], []
     with open(fname) as f:
         for line in f:
@@ -130,3 +132,4 @@ def barycentric_coordinates(points: torch.Tensor, A: torch.Tensor, B: torch.Tens
 
 
 from .compute_sdf import compute_sdf, closest_point, closest_point_on_triangle     # noqa: E402
+from .texture import TextureBank, closest_tex, sample_tex                            # noqa: E402
