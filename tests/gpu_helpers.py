@@ -126,6 +126,16 @@ def _decoder_pair(bias=True, in_dim=32, hidden=64):
 
 
 def _check_fused_decoder(mode, io_dtype, tol, bias, in_dim, hidden, S):
+    """The fused decoder against the fp32 torch modules at REALISTIC MAGNITUDES ONLY: random normal features and weights, unit view
+    directions, so that the bf16 rounding of operands, the sine / input columns of the view embedding and saturating sigmoids are
+    exercised.  Its bars are statistical (bf16: atol on rgb, relative L2 per gradient tensor against what torch autocast loses; fp32:
+    3e-4 of a tensor's maximum) and cannot see a single wrong element.  Element-wise correctness is owned by the exact-arithmetic
+    tests (tests/test_gpu_decoder_exact.py, bit for bit against float64).  They compare every element of density, grad_feats and
+    grad_params; over their patterns every weight and bias is non-zero at least once in the forward (in the paired mode, the
+    only one with a live colour backward, 74 % of W4, 93 % of W3 and 84 % of W2), and every element of grad_params is non-zero
+    at least once except the dW3 columns of the embedding's input and sine columns, which are exactly 0 at direction 0.  They also
+    own: dead lanes of the tail tile, every tile's hand-over, `grad_params +=`, b2 entering before the bf16 pack, the narrow-row
+    loads / stores at widths 1, 5, 12, 31 and 32 and the rows behind the end of grad_feats."""
     from wisp.ops.nerf_mlp import fused_nerf_decoder, supports
     nef = _decoder_pair(bias, in_dim, hidden)
     nef.decoder_compute = mode
