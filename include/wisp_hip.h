@@ -38,7 +38,7 @@ const char* wisp_last_error(void);
  * slot scales of the hash-grid backward; 4 = round 4: workspace + row counts of the order-free trilinear / codebook backward.
  * Entry points that are only ADDED - wisp_spc_query_chain, wisp_composite_loss, wisp_codebook_trilinear_multi_bwd,
  * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
- * wisp_mesh_closest_tex, wisp_mesh_sample_tex - do not bump it). */
+ * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -337,6 +337,25 @@ int wisp_sdf_train_step(const float* coords, const float* gts, int64_t n, const 
                         const float* w2, const float* b2, int hidden, float* const* grad_feats, float* grad_w1, float* grad_b1,
                         float* grad_w2, float* grad_b2, float* loss, void* scratch, int64_t scratch_bytes, void* workspace,
                         int64_t workspace_bytes, wisp_stream_t stream);
+
+/* The same step for a NeuralSDFTex (wisp/models/nefs/neural_sdf_tex.py:95-123: four decoder outputs, rgb = sigmoid(y[0:3]),
+ * sdf = y[3]) as the reference's SDFTrainer.step takes it with sample_tex and only_last (wisp/trainers/sdf_trainer.py:65-124):
+ *     loss = (sum((rgb - rgb_gt)^2) + sum((sdf - gt)^2)) / n
+ * replacing the query, the per-level lookups, two GEMMs with their elementwise companions, the sigmoid, the loss and all of
+ * that again backwards by four launches.  Arguments as for wisp_sdf_train_step, plus:
+ *  rgb_gts f32 [n,3] (row stride 3); pos_input 1: the decoder input is [position, features] (w1 [hidden, 19]), 0: the features
+ *  alone (w1 [hidden, 16]); w2 f32 [4, hidden], b2 [4] and their gradients (ADDED to);
+ *  loss f32 [3] is written: {total / n, sum((sdf - gt)^2), sum((rgb - rgb_gt)^2)} - the two un-normalised sums are what the
+ *  reference's tracker accumulates as l2_loss / rgb_loss (sdf_trainer.py:115-117).
+ *  channels must be 16, 1 <= hidden <= 256, num_lods <= 16; wisp_sdf_tex_train_scratch_bytes returns -1 for anything else.
+ * Bitwise repeatable: every sum has a fixed order or is an integer sum. */
+int64_t wisp_sdf_tex_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int pos_input);
+int wisp_sdf_tex_train_step(const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
+                            const int32_t* exsum, const int16_t* points, const int32_t* trinkets, const float* const* feats,
+                            const int32_t* levels, const int64_t* rows, int num_lods, int channels, int half_round, int pos_input,
+                            const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
+                            float* const* grad_feats, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, float* loss,
+                            void* scratch, int64_t scratch_bytes, void* workspace, int64_t workspace_bytes, wisp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Raymarch sample generation  (replace OctreeAS._raymarch_ray / _raymarch_voxel / _raymarch_uniform,

@@ -1033,3 +1033,313 @@ extern "C" int wisp_sdf_train_step(const float* coords, const float* gts, int64_
     WISP_CHECK_LAUNCH();
     return WISP_OK;
 }
+
+// ------------------------------------------------------------------------------------- fused textured SDF regression step
+// The same step for a NeuralSDFTex (wisp/models/nefs/neural_sdf_tex.py:95-123; sdf_trainer.py:65-124 with sample_tex and
+// only_last): the decoder has four outputs, rgb = sigmoid(y[0:3]), sdf = y[3], and the embedded position is optional:
+//     in = pos_input ? [x, f] : f ;  loss = (sum (rgb - rgb_gt)^2 + sum (sdf - gt)^2) / B
+//   sdf_tex_train_kernel         phase 1 is sdf_train_kernel's, statement for statement (bit-identical features); phase 2 keeps
+//                                four output dot products per lane, reduces them by the same butterfly, and forms
+//                                g_o = 2 diff_o sigmoid'(y_o) / B (colour), g_3 = 2 diff_3 / B (distance),
+//                                d pre-activation[h] = (a_h > 0) sum_o W2[o][h] g_o in ascending o; phase 3 owns
+//                                dW1 [H][in_dim], db1 [H], dW2 [4][H], db2 [4] and three scalars (squared distance error,
+//                                squared colour error, their total), one thread per entry, samples in order.
+//   sdf_tex_train_reduce_kernel  adds the partial rows in workgroup order, ADDS to the gradient tensors, writes
+//                                loss[3] = {total / B, distance sum, colour sum}.
+// With inert colour rows (W2[0:3] = 0, b2[0:3] = 0, colour target 0.5: g_0..2 = 0 exactly) every sum that reaches dW1, db1 and
+// the feature tables is the one-output kernel's, term by term in the same order: those gradients are bitwise equal.
+struct StTexField {
+    const float* feats[SG_MAX_LODS];
+    int32_t level[SG_MAX_LODS];
+    int num_lods, channels, half_round, hidden, max_level, pos_input;
+    const float *w1, *b1, *w2, *b2;
+};
+
+static inline int st_tex_entries(int hidden, int in_dim) { return hidden * in_dim + 5 * hidden + 4 + 3; }
+
+__global__ void __launch_bounds__(ST_GROUP * ST_GROUPS)
+sdf_tex_train_kernel(const float* __restrict__ coords, const float* __restrict__ gts, const float* __restrict__ rgb_gts, int64_t n,
+                     const uint8_t* __restrict__ octree, const int32_t* __restrict__ exsum, const int16_t* __restrict__ points,
+                     const int32_t* __restrict__ trinkets, StTexField fld, float inv_batch,
+                     float* __restrict__ partials /* [grid][row] */, int row_stride, float* __restrict__ dfeat /* [n][channels] */,
+                     int64_t* __restrict__ chain /* [n][num_lods] */, SgHeader* __restrict__ hdr) {
+    extern __shared__ float s_stx[];
+    const int C = fld.channels, H = fld.hidden, NL = fld.num_lods;
+    const int fo = fld.pos_input ? 3 : 0;               // first feature column of the decoder input
+    const int in_dim = fo + C;
+    const int in_pad = in_dim | 1;                      // odd row stride: the lanes of a group read different rows
+    const int spb = ST_GROUPS / NL;                     // samples per workgroup pass: one lane group per (sample, level)
+    float* s_w1 = s_stx;                                // [H][in_pad]
+    float* s_b1 = s_w1 + H * in_pad;                    // [H]
+    float* s_w2 = s_b1 + H;                             // [4][H]
+    float* s_in = s_w2 + 4 * H;                         // [spb][in_dim]        decoder inputs of the pass
+    float* s_ga = s_in + ST_GROUPS * in_dim;            // [spb][H]             d loss / d pre-activation
+    float* s_r = s_ga + ST_GROUPS * H;                  // [spb][H]             relu output (for d W2)
+    float* s_g = s_r + ST_GROUPS * H;                   // [spb][4]             d loss / d y
+    float* s_sq = s_g + ST_GROUPS * 4;                  // [spb][2]             squared distance error, squared colour error
+    float* s_lev = s_sq + ST_GROUPS * 2;                // [groups][C]          one level's lookup of one sample
+    float* s_wm = s_lev + ST_GROUPS * ST_GROUP;         // [groups]             its largest corner weight
+    for (int e = threadIdx.x; e < H * in_dim; e += blockDim.x) s_w1[(e / in_dim) * in_pad + e % in_dim] = fld.w1[e];
+    for (int e = threadIdx.x; e < H; e += blockDim.x) s_b1[e] = fld.b1[e];
+    for (int e = threadIdx.x; e < 4 * H; e += blockDim.x) s_w2[e] = fld.w2[e];
+    const int c = threadIdx.x & (ST_GROUP - 1);
+    const int grp = threadIdx.x / ST_GROUP;
+    const int L = fld.max_level;
+    const float b2[4] = {fld.b2[0], fld.b2[1], fld.b2[2], fld.b2[3]};
+    // partial sums of this workgroup: d W1 [H][in_dim], d b1 [H], d W2 [4][H], d b2 [4], distance / colour / total squared error -
+    // in that order; every entry has one owner
+    const int o_b1 = H * in_dim, o_w2 = o_b1 + H, o_b2 = o_w2 + 4 * H, o_sq = o_b2 + 4;
+    const int n_entries = o_sq + 3;
+    float* s_own = s_wm + ST_GROUPS;                    // [n_entries]
+    for (int e = threadIdx.x; e < n_entries; e += blockDim.x) s_own[e] = 0.0f;
+    uint32_t mbits = 0;
+    const int my_si = grp / NL, my_li = grp - my_si * NL;                 // phase 1: this group's (sample of the pass, level)
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * spb; base < n; base += (int64_t)gridDim.x * spb) {
+        // ---- phase 1: sdf_train_kernel's, statement for statement
+        {
+            const int64_t s = base + my_si;
+            float acc = 0.0f, wm = 0.0f;
+            if (my_si < spb && s < n) {
+                const float px = coords[s * 3], py = coords[s * 3 + 1], pz = coords[s * 3 + 2];
+                const bool inside = (fabsf(px) <= 1.0f) && (fabsf(py) <= 1.0f) && (fabsf(pz) <= 1.0f);
+                const float res = (float)(1 << L);
+                const int top = (1 << L) - 1;
+                const int qx = min((int)floorf(res * (0.5f * px + 0.5f)), top);
+                const int qy = min((int)floorf(res * (0.5f * py + 0.5f)), top);
+                const int qz = min((int)floorf(res * (0.5f * pz + 0.5f)), top);
+                const float pos[3] = {px, py, pz};
+                const int lv = fld.level[my_li];
+                int64_t node = inside ? 0 : -1;
+                for (int l = 0; l < lv && node >= 0; ++l) {               // (spc_query_kernel's walk)
+                    const int cs = st_child_slot(qx, qy, qz, L - 1 - l);
+                    const uint32_t bits = octree[node];                   // both loads of a level go out together: one round
+                    const int64_t first = (int64_t)exsum[node];           // trip per level, not two
+                    const int64_t child = first + __popc(bits & ((2u << cs) - 1u));
+                    node = ((bits >> cs) & 1u) ? child : -1;
+                }
+                if (c == 0) chain[s * NL + my_li] = node;
+                if (node >= 0) {
+                    float w[8];
+                    sg_coeffs(pos, points + node * 3, lv, w);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) wm = fmaxf(wm, fabsf(w[j]));
+                    const int32_t* tr = trinkets + node * 8;
+                    const float* f = fld.feats[my_li];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        float fv = f[(int64_t)tr[j] * C + c];
+                        if (fld.half_round) fv = __half2float(__float2half_rn(fv));
+                        acc += fv * w[j];
+                    }
+                    if (fld.half_round) acc = __half2float(__float2half_rn(acc));
+                }
+            }
+            s_lev[grp * ST_GROUP + c] = acc;
+            if (c == 0) s_wm[grp] = wm;
+        }
+        __syncthreads();
+        // ---- phase 2: group si owns sample si of the pass: decoder forward, d loss / d y, decoder backward
+        const int64_t s = base + grp;
+        const bool live = grp < spb && s < n;
+        float* gin = s_in + grp * in_dim;
+        float* ga = s_ga + grp * H;
+        float* gr = s_r + grp * H;
+        float wmax = 0.0f;
+        if (live) {
+            float feat = 0.0f;                                            // channel c, summed over the levels in order
+            for (int li = 0; li < NL; ++li) {
+                feat += s_lev[(grp * NL + li) * ST_GROUP + c];
+                wmax = fmaxf(wmax, s_wm[grp * NL + li]);
+            }
+            if (c < fo) gin[c] = coords[s * 3 + c];
+            gin[fo + c] = feat;
+        }
+        __builtin_amdgcn_wave_barrier();                 // a group's lanes are in one wave: LDS order suffices
+        if (live) {
+            // decoder forward: in = [position, features] (neural_sdf_tex.py: embedded position first) or the features alone
+            float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
+            for (int hh = c; hh < H; hh += ST_GROUP) {
+                const float* wr = s_w1 + hh * in_pad;
+                float a = s_b1[hh];
+                for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
+                const float r = fmaxf(a, 0.0f);
+                o0 = __builtin_fmaf(s_w2[hh], r, o0);
+                o1 = __builtin_fmaf(s_w2[H + hh], r, o1);
+                o2 = __builtin_fmaf(s_w2[2 * H + hh], r, o2);
+                o3 = __builtin_fmaf(s_w2[3 * H + hh], r, o3);
+                ga[hh] = a > 0.0f ? 1.0f : 0.0f;        // the relu mask; finished below, once d loss / d y is known
+                gr[hh] = r;
+            }
+#pragma unroll
+            for (int d = ST_GROUP / 2; d >= 1; d >>= 1) {
+                o0 += __shfl_xor(o0, d, ST_GROUP);
+                o1 += __shfl_xor(o1, d, ST_GROUP);
+                o2 += __shfl_xor(o2, d, ST_GROUP);
+                o3 += __shfl_xor(o3, d, ST_GROUP);
+            }
+            const float c0 = 1.0f / (1.0f + expf(-(o0 + b2[0])));
+            const float c1 = 1.0f / (1.0f + expf(-(o1 + b2[1])));
+            const float c2 = 1.0f / (1.0f + expf(-(o2 + b2[2])));
+            const float d0 = c0 - rgb_gts[s * 3], d1 = c1 - rgb_gts[s * 3 + 1], d2 = c2 - rgb_gts[s * 3 + 2];
+            const float d3 = (o3 + b2[3]) - gts[s];
+            const float g0 = 2.0f * d0 * (c0 * (1.0f - c0)) * inv_batch;      // d loss / d y_o through the sigmoid
+            const float g1 = 2.0f * d1 * (c1 * (1.0f - c1)) * inv_batch;
+            const float g2 = 2.0f * d2 * (c2 * (1.0f - c2)) * inv_batch;
+            const float g3 = 2.0f * d3 * inv_batch;                           // d [sum (sdf - gt)^2 / B] / d sdf
+            for (int hh = c; hh < H; hh += ST_GROUP) {
+                float t = __builtin_fmaf(s_w2[hh], g0, 0.0f);
+                t = __builtin_fmaf(s_w2[H + hh], g1, t);
+                t = __builtin_fmaf(s_w2[2 * H + hh], g2, t);
+                t = __builtin_fmaf(s_w2[3 * H + hh], g3, t);
+                ga[hh] = ga[hh] != 0.0f ? t : 0.0f;
+            }
+            if (c == 0) {
+                s_g[grp * 4] = g0; s_g[grp * 4 + 1] = g1; s_g[grp * 4 + 2] = g2; s_g[grp * 4 + 3] = g3;
+                s_sq[grp * 2] = d3 * d3;
+                s_sq[grp * 2 + 1] = (d0 * d0 + d1 * d1) + d2 * d2;
+            }
+        } else if (grp < spb) {
+            for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = 0.0f; gr[hh] = 0.0f; }
+            if (c < fo) gin[c] = 0.0f;
+            gin[fo + c] = 0.0f;
+            if (c < 4) s_g[grp * 4 + c] = 0.0f;
+            if (c < 2) s_sq[grp * 2 + c] = 0.0f;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (live) {
+            // gradient of the decoder input, feature columns only (nothing consumes d / d position)
+            float dx = 0.0f;
+            for (int hh = 0; hh < H; ++hh) dx = __builtin_fmaf(ga[hh], s_w1[hh * in_pad + fo + c], dx);
+            dfeat[s * C + c] = dx;
+            const uint32_t b = __float_as_uint(wmax * fabsf(dx)) & 0x7fffffffu;
+            const uint32_t nb = (!(dx == dx) || !(wmax == wmax)) ? 0x7fc00000u : b;
+            mbits = nb > mbits ? nb : mbits;
+        }
+        __syncthreads();
+        // ---- phase 3: weight gradients of this pass: the thread that owns an entry adds the samples up in order
+        for (int e = threadIdx.x; e < n_entries; e += blockDim.x) {
+            float acc = 0.0f;
+            if (e < o_b1) {
+                const int hh = e / in_dim, i = e - hh * in_dim;
+                for (int q = 0; q < spb; ++q) acc = __builtin_fmaf(s_ga[q * H + hh], s_in[q * in_dim + i], acc);
+            } else if (e < o_w2) {
+                const int hh = e - o_b1;
+                for (int q = 0; q < spb; ++q) acc += s_ga[q * H + hh];
+            } else if (e < o_b2) {
+                const int o = (e - o_w2) / H, hh = (e - o_w2) - o * H;
+                for (int q = 0; q < spb; ++q) acc = __builtin_fmaf(s_g[q * 4 + o], s_r[q * H + hh], acc);
+            } else if (e < o_sq) {
+                for (int q = 0; q < spb; ++q) acc += s_g[q * 4 + (e - o_b2)];
+            } else if (e < o_sq + 2) {
+                for (int q = 0; q < spb; ++q) acc += s_sq[q * 2 + (e - o_sq)];
+            } else {
+                for (int q = 0; q < spb; ++q) acc += s_sq[q * 2 + 1] + s_sq[q * 2];
+            }
+            s_own[e] += acc;
+        }
+        __syncthreads();
+    }
+    for (int e = threadIdx.x; e < n_entries; e += blockDim.x) partials[(int64_t)blockIdx.x * row_stride + e] = s_own[e];
+    mbits = sg_wave_umax(mbits);
+    if ((threadIdx.x & 63) == 0 && mbits > __atomic_load_n(&hdr->absmax_bits, __ATOMIC_RELAXED)) atomicMax(&hdr->absmax_bits, mbits);
+}
+
+__global__ void __launch_bounds__(256)
+sdf_tex_train_reduce_kernel(const float* __restrict__ partials, int rows, int row_stride, int H, int in_dim, float* __restrict__ gw1,
+                            float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2, float* __restrict__ loss,
+                            float inv_batch) {
+    // 16 lanes per entry: lane r adds rows r, r + 16, ... in order, then a fixed butterfly over the 16 lanes
+    const int o_b1 = H * in_dim, o_w2 = o_b1 + H, o_b2 = o_w2 + 4 * H, o_sq = o_b2 + 4;
+    const int n_entries = o_sq + 3;
+    const int r0 = threadIdx.x & 15;
+    for (int e = blockIdx.x * 16 + (threadIdx.x >> 4); e < n_entries + 15; e += gridDim.x * 16) {      // (whole groups stay together)
+        const bool in = e < n_entries;
+        float acc = 0.0f;
+        if (in)
+            for (int r = r0; r < rows; r += 16) acc += partials[(int64_t)r * row_stride + e];
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 16);
+        if (!in || r0 != 0) continue;
+        if (e < o_b1) gw1[e] += acc;
+        else if (e < o_w2) gb1[e - o_b1] += acc;
+        else if (e < o_b2) gw2[e - o_w2] += acc;
+        else if (e < o_sq) gb2[e - o_b2] += acc;
+        else if (e == o_sq) loss[1] = acc;                                  // un-normalised: what the tracker adds up as l2_loss
+        else if (e == o_sq + 1) loss[2] = acc;                              // ... as rgb_loss
+        else loss[0] = acc * inv_batch;
+    }
+}
+
+static inline int st_tex_row_stride(int hidden, int in_dim) { return (st_tex_entries(hidden, in_dim) + 15) / 16 * 16; }
+
+extern "C" int64_t wisp_sdf_tex_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int pos_input) {
+    if (n < 0 || num_lods < 1 || num_lods > SG_MAX_LODS || channels != ST_GROUP || hidden < 1 || hidden > ST_MAX_HIDDEN ||
+        (pos_input != 0 && pos_input != 1))
+        return -1;
+    return (int64_t)st_grid(n, num_lods) * st_tex_row_stride(hidden, (pos_input ? 3 : 0) + channels) * 4 + sg_round64(n * channels * 4) +
+           n * num_lods * 8;
+}
+
+extern "C" int wisp_sdf_tex_train_step(const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
+                                       const int32_t* exsum, const int16_t* points, const int32_t* trinkets,
+                                       const float* const* feats, const int32_t* levels, const int64_t* rows, int num_lods,
+                                       int channels, int half_round, int pos_input, const float* w1, const float* b1,
+                                       const float* w2, const float* b2, int hidden, float* const* grad_feats, float* grad_w1,
+                                       float* grad_b1, float* grad_w2, float* grad_b2, float* loss, void* scratch,
+                                       int64_t scratch_bytes, void* workspace, int64_t workspace_bytes, wisp_stream_t stream) {
+    WISP_REQUIRE(n >= 1 && num_lods >= 1 && num_lods <= SG_MAX_LODS, "bad sizes");
+    WISP_REQUIRE(channels == ST_GROUP, "the fused textured SDF step is built for 16 feature channels");
+    WISP_REQUIRE(hidden >= 1 && hidden <= ST_MAX_HIDDEN, "hidden width out of range");
+    WISP_REQUIRE(pos_input == 0 || pos_input == 1, "pos_input must be 0 or 1");
+    WISP_REQUIRE(coords && gts && rgb_gts && octree && exsum && points && trinkets && feats && levels && rows && w1 && b1 && w2 &&
+                 b2 && grad_feats && grad_w1 && grad_b1 && grad_w2 && grad_b2 && loss && scratch && workspace, "null pointer");
+    WISP_REQUIRE(scratch_bytes >= wisp_sdf_tex_train_scratch_bytes(n, num_lods, channels, hidden, pos_input),
+                 "scratch too small (wisp_sdf_tex_train_scratch_bytes)");
+    StTexField fld;
+    SgLods ml;
+    WISP_REQUIRE(sg_fill(ml, levels, rows, num_lods) == 0, "bad level or row count");
+    for (int l = 0; l < num_lods; ++l) {
+        WISP_REQUIRE(feats[l] && grad_feats[l] && (l == 0 || levels[l] > levels[l - 1]), "bad level list");
+        fld.feats[l] = feats[l]; fld.level[l] = levels[l]; ml.grad[l] = grad_feats[l];
+    }
+    fld.num_lods = num_lods; fld.channels = channels; fld.half_round = half_round; fld.hidden = hidden;
+    fld.max_level = levels[num_lods - 1]; fld.pos_input = pos_input;
+    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
+    const SgPlan pl = sg_plan(ml.base[num_lods], channels, 0);
+    WISP_REQUIRE(workspace_bytes >= pl.bytes, "workspace too small (wisp_spc_bwd_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    SgHeader* hdr = reinterpret_cast<SgHeader*>(ws);
+    const int in_dim = (pos_input ? 3 : 0) + channels;
+    const int grid = st_grid(n, num_lods), row_stride = st_tex_row_stride(hidden, in_dim), n_entries = st_tex_entries(hidden, in_dim);
+    float* partials = static_cast<float*>(scratch);
+    float* dfeat = partials + (size_t)grid * row_stride;
+    int64_t* chain = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(dfeat) + sg_round64(n * channels * 4));
+    const size_t lds = ((size_t)hidden * (in_dim | 1) + 5 * hidden + (size_t)ST_GROUPS * (in_dim + 2 * hidden + 4 + 2 + ST_GROUP + 1) +
+                        (size_t)n_entries) * 4;
+    const float inv_batch = 1.0f / (float)n;
+    if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, __func__, "hipMemsetAsync failed");
+    if (const hipError_t e = WISP_ALLOW_LDS(sdf_tex_train_kernel, lds)) return wisp_fail(WISP_ERR_LAUNCH, __func__, hipGetErrorString(e));
+    hipLaunchKernelGGL(sdf_tex_train_kernel, dim3(grid), dim3(ST_GROUP * ST_GROUPS), lds, s, coords, gts, rgb_gts, n, octree, exsum,
+                       points, trinkets, fld, inv_batch, partials, row_stride, dfeat, chain, hdr);
+    hipLaunchKernelGGL(sdf_tex_train_reduce_kernel, dim3((n_entries + 15) / 16), dim3(256), 0, s, partials, grid, row_stride, hidden,
+                       in_dim, grad_w1, grad_b1, grad_w2, grad_b2, loss, inv_batch);
+    // the corner sums: the magnitude bound is in the header already (sdf_tex_train_kernel), so only scatter + row pass
+    SgCall c{coords, chain, 1, num_lods, 1, points, trinkets, dfeat, n, num_lods, channels, 1, channels};
+    uint8_t* flags = sg_use_flags(c, pl) ? ws + pl.off_flags : nullptr;
+    long long* acc = reinterpret_cast<long long*>(ws + pl.off_acc);
+    const int clog = sg_clog(n);
+    const int split = sg_split_lods(c);
+    hipLaunchKernelGGL((spc_grad_scatter_wide_kernel<int64_t>),
+                       dim3((unsigned)min64(ceil_div64(n * (split ? num_lods : 1), 256 / channels), 16384)), dim3(256), 0, s, coords, chain,
+                       (int64_t)num_lods, 1, points, trinkets, ml, dfeat, n, num_lods, channels, 1, clog, pl.stride, channels, hdr, flags,
+                       acc, split);
+    int lpr = 1;
+    while (lpr < channels && lpr < 64) lpr <<= 1;
+    if (pl.total_rows > 0)
+        hipLaunchKernelGGL(spc_grad_finalize_kernel, dim3((unsigned)min64(ceil_div64(pl.total_rows, 256 / lpr), 8192)), dim3(256), 0, s, ml,
+                           num_lods, channels, pl.stride, lpr, clog, hdr, flags, acc);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}

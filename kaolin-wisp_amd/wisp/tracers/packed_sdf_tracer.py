@@ -77,11 +77,18 @@ class PackedSDFTracer(BaseTracer):
     def _fused_field(nef, lod_idx):
         """The tensors wisp_sdf_trace_step_fused needs, or None when the field is not the shape it is built for: a plain
         NeuralSDF (nglod_octree.yaml) - OctreeGrid with 16 'sum'-med feature channels, linear interpolation, raw position
-        input without embedding, one hidden relu layer with bias.  Anything else marches through `nef(...)` per iteration."""
+        input without embedding, one hidden relu layer with bias.  A NeuralSDFTex of the same shape (four outputs; features
+        alone, or the raw position in front of them) marches on its fourth output row.  Anything else marches through
+        `nef(...)` per iteration."""
         from wisp.models.grids.octree_grid import OctreeGrid
         from wisp.models.nefs.neural_sdf import NeuralSDF
+        from wisp.models.nefs.neural_sdf_tex import NeuralSDFTex
         import os
-        if os.environ.get("WISP_SDF_FUSED", "1") == "0" or type(nef) is not NeuralSDF or type(nef.grid) is not OctreeGrid:
+        if os.environ.get("WISP_SDF_FUSED", "1") == "0" or type(nef.grid) is not OctreeGrid:
+            return None
+        if type(nef) is NeuralSDFTex:
+            return PackedSDFTracer._fused_field_tex(nef, lod_idx)
+        if type(nef) is not NeuralSDF:
             return None
         g, dec = nef.grid, nef.decoder
         if (g.multiscale_type != 'sum' or g.interpolation_type != 'linear' or g.feature_dim != 16 or lod_idx < 1
@@ -99,6 +106,36 @@ class PackedSDFTracer(BaseTracer):
         return dict(feats=feats, levels=[int(l) for l in g.active_lods[:n]], half_round=bool(g.half_features),
                     w1=dec.layers[0].weight.detach().float().contiguous(), b1=dec.layers[0].bias.detach().float().contiguous(),
                     w2=dec.lout.weight.detach().float().reshape(-1).contiguous(), b2=dec.lout.bias.detach().float().contiguous(),
+                    octree=g.blas.octree, exsum=g.blas.prefix, points=g.blas.points, trinkets=g.trinkets.int().contiguous())
+
+    @staticmethod
+    def _fused_field_tex(nef, lod_idx):
+        """_fused_field for a NeuralSDFTex: the distance is the decoder's fourth output, so the kernel gets that row of the
+        output layer; the colour rows are not needed to march."""
+        g, dec = nef.grid, nef.decoder
+        with_pos = bool(nef.position_input)
+        if (g.multiscale_type != 'sum' or g.interpolation_type != 'linear' or g.feature_dim != 16 or lod_idx < 1
+                or (with_pos and not (isinstance(nef.pos_embedder, torch.nn.Identity) and nef.pos_embed_dim == 3))
+                or (not with_pos and nef.embedder_type != 'none')
+                or nef.activation_type != 'relu' or nef.num_layers != 1 or len(dec.layers) != 1 or dec.skip
+                or type(dec.layers[0]) is not torch.nn.Linear or type(dec.lout) is not torch.nn.Linear
+                or dec.layers[0].bias is None or dec.lout.bias is None or dec.lout.out_features != 4
+                or dec.layers[0].out_features > 256 or dec.layers[0].in_features != (3 if with_pos else 0) + 16
+                or not g.features[0].is_cuda):
+            return None
+        n = lod_idx + 1
+        feats = [g.features[i].detach().contiguous() for i in range(n)]
+        if any(f.dtype != feats[0].dtype or f.shape[1] != 16 for f in feats):
+            return None
+        g._sync_device(feats[0].device)
+        w1 = dec.layers[0].weight.detach().float()
+        if not with_pos:
+            # the kernel's input layout is [position, features]: three zero columns in front make the position's share of every
+            # dot product fmaf(0, x, a) == a exactly for the finite coordinates a march produces - the feature-only result
+            w1 = torch.cat([torch.zeros(w1.shape[0], 3, dtype=w1.dtype, device=w1.device), w1], dim=1)
+        return dict(feats=feats, levels=[int(l) for l in g.active_lods[:n]], half_round=bool(g.half_features),
+                    w1=w1.contiguous(), b1=dec.layers[0].bias.detach().float().contiguous(),
+                    w2=dec.lout.weight.detach().float()[3].contiguous(), b2=dec.lout.bias.detach().float()[3:4].contiguous(),
                     octree=g.blas.octree, exsum=g.blas.prefix, points=g.blas.points, trinkets=g.trinkets.int().contiguous())
 
     def _march_fused(self, fld, rays, rt_pidx, depth, st, num_steps, step_size, min_dis):

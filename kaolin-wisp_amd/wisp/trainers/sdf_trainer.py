@@ -3,6 +3,10 @@ plumbing - regression of a signed-distance field on (coordinate, distance) pairs
 
     loss = sum over the loss LODs of  sum((nef(coords, lod)['sdf'] - gts)^2) / batch      (only_last: the finest LOD alone)
 
+and, for a field that answers 'rgb' and 'sdf' together (NeuralSDFTex; the reference's branch for a dataset with sample_tex), of
+(coordinate, distance, colour) triples: the colour term sum((rgb_pred - rgb)^2) joins the loss (accumulated as the reference
+accumulates it, see _forward_backward).
+
 Parameter groups, learning-rate weighting and the fused single-launch optimizer over one flat parameter buffer are the
 MultiviewTrainStep's (base_trainer.py:205-235); nglod_octree.yaml trains with Adam, lr 1e-3, eps 1e-15, grid lr x 1."""
 import logging as log
@@ -31,6 +35,9 @@ class SDFTrainStep:
         self.alpha, self.momentum = alpha, momentum
         self.only_last = only_last
         self.opt_steps = 0
+        # a field whose forward registers 'rgb' and 'sdf' together (NeuralSDFTex): step() then needs the colour ground truth
+        self.textured = any({"rgb", "sdf"} <= set(ch) for ch in getattr(nef, "_forward_functions", {}).values())
+        self.last_l2 = self.last_rgb = None       # after a textured step: the two un-normalised sums (device tensors, no sync)
 
     def loss_lods(self):
         lods = list(range(self.nef.grid.num_lods))
@@ -55,7 +62,9 @@ class SDFTrainStep:
     def _fused_field(self):
         """What wisp_sdf_train_step needs, or None when this field is not its shape: NeuralSDF's decoder (one hidden relu layer,
         biases, one output) over [position, 'sum' OctreeGrid features of 16 channels], fp32 parameters living in the flat
-        buffers, loss on the finest LOD only.  WISP_SDF_TRAIN_FUSED=0 keeps the modular launches."""
+        buffers, loss on the finest LOD only.  A NeuralSDFTex (four outputs; features alone, or the identity position in front
+        of them) gets what wisp_sdf_tex_train_step needs under the same gates.  WISP_SDF_TRAIN_FUSED=0 keeps the modular
+        launches."""
         import os
         if getattr(self, "_fused_seen_only_last", None) != self.only_last:        # toggled since the decision was taken
             self._fused_cache, self._fused_seen_only_last = None, self.only_last
@@ -77,6 +86,8 @@ class SDFTrainStep:
         grid, dec = getattr(nef, "grid", None), getattr(nef, "decoder", None)
         if type(grid) is not OctreeGrid or type(getattr(grid, "blas", None)) is not OctreeAS or dec is None:
             return None
+        if self.textured:
+            return self._fused_field_tex(grid, dec)
         if not (grid.interpolation_type == 'linear' and grid.multiscale_type == 'sum' and grid.feature_dim == 16 and grid._fusable()
                 and 1 <= grid.num_lods <= 16 and type(getattr(nef, "pos_embedder", None)) is torch.nn.Identity
                 and getattr(nef, "position_input", False)):
@@ -89,6 +100,37 @@ class SDFTrainStep:
                    and q.grad.dtype == torch.float32 for q in prm):
             return None
         self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm)
+        return self._fused_cache
+
+    def _fused_field_tex(self, grid, dec):
+        """The textured branch of _fused_field (the grid / accelerator types are checked by the caller)."""
+        from wisp.models.nefs._grid_mlp import BasicDecoder
+        from wisp.models.nefs.neural_sdf_tex import NeuralSDFTex
+        nef = self.nef
+        if type(nef) is not NeuralSDFTex:
+            return None
+        if not (grid.interpolation_type == 'linear' and grid.multiscale_type == 'sum' and grid.feature_dim == 16 and grid._fusable()
+                and 1 <= grid.num_lods <= 16):
+            return None
+        if nef.embedder_type == 'none' and not nef.position_input:
+            pos = 0
+        elif type(getattr(nef, "pos_embedder", None)) is torch.nn.Identity and nef.position_input and nef.pos_embed_dim == 3:
+            pos = 1
+        else:
+            return None
+        # (the shape check of _fusable_small_decoder, restated for four outputs: that function serves the one-output `decode`)
+        layers, lout = getattr(dec, 'layers', None), getattr(dec, 'lout', None)
+        if not (self.flat.data.is_cuda and type(dec) is BasicDecoder and layers is not None and len(layers) == 1 and not dec.skip
+                and type(layers[0]) is torch.nn.Linear and type(lout) is torch.nn.Linear and layers[0].bias is not None
+                and lout.bias is not None and lout.out_features == 4 and 1 <= layers[0].out_features <= 256
+                and lout.in_features == layers[0].out_features and layers[0].in_features == 3 * pos + grid.feature_dim
+                and dec.activation in (torch.relu, torch.nn.functional.relu)):
+            return None
+        prm = list(grid.features[:grid.num_lods]) + [layers[0].weight, layers[0].bias, lout.weight, lout.bias]
+        if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.grad is not None and q.grad.is_contiguous()
+                   and q.grad.dtype == torch.float32 for q in prm):
+            return None
+        self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm, tex=True, pos=pos)
         return self._fused_cache
 
     def _fused_still_valid(self, c):
@@ -106,7 +148,7 @@ class SDFTrainStep:
                 return False
         return True
 
-    def _forward_backward(self, coords, gts):
+    def _forward_backward(self, coords, gts, rgb=None):
         fused = self._fused_field() if coords.is_cuda and coords.ndim == 2 and coords.shape[0] > 0 else None
         if fused is not None:
             C = _hip()
@@ -116,10 +158,33 @@ class SDFTrainStep:
             grid._sync_device(coords.device)
             tr = grid.trinkets if grid.trinkets.dtype == torch.int32 else grid.trinkets.int()
             w1, b1, w2, b2 = dec.layers[0].weight, dec.layers[0].bias, dec.lout.weight, dec.lout.bias
+            if fused.get("tex"):
+                colour = rgb[..., :3].reshape(-1, 3).to(torch.float32).contiguous()
+                out = C.sdf_tex_train_step(coords, gts, colour, blas.octree, blas.prefix, blas.points, tr,
+                                           [f.detach() for f in grid.features[:L]], grid.active_lods[:L], grid.half_features,
+                                           fused["pos"], w1.detach(), b1.detach(), w2.detach(), b2.detach(),
+                                           [f.grad for f in grid.features[:L]], w1.grad, b1.grad, w2.grad, b2.grad)
+                self.last_l2, self.last_rgb = out[1], out[2]
+                return out[0]
             loss = C.sdf_train_step(coords, gts, blas.octree, blas.prefix, blas.points, tr, [f.detach() for f in grid.features[:L]],
                                     grid.active_lods[:L], grid.half_features, w1.detach(), b1.detach(), w2.detach(), b2.detach(),
                                     [f.grad for f in grid.features[:L]], w1.grad, b1.grad, w2.grad, b2.grad)
             return loss[0]
+        if self.textured:
+            # SDFTrainer.step with sample_tex: the running colour sum joins the loss INSIDE the LOD loop, as the reference does
+            loss, l2_loss, rgb_loss = 0.0, 0.0, 0.0
+            last_l2 = last_rgb = None
+            preds = [self.nef(coords=coords, lod_idx=lod_idx, channels=["rgb", "sdf"]) for lod_idx in self.loss_lods()]
+            for colour, dist in preds:
+                last_rgb = ((colour - rgb[..., :3]) ** 2).sum()
+                rgb_loss = rgb_loss + last_rgb
+                last_l2 = ((dist - gts) ** 2).sum()
+                l2_loss = l2_loss + last_l2
+                loss = loss + rgb_loss
+            loss = (loss + l2_loss) / coords.shape[0]
+            loss.backward()
+            self.last_l2, self.last_rgb = last_l2.detach(), last_rgb.detach()
+            return loss.detach()
         loss = 0.0
         for lod_idx in self.loss_lods():
             pred = self.nef(coords=coords, lod_idx=lod_idx, channels="sdf")
@@ -141,41 +206,56 @@ class SDFTrainStep:
         self._fused_cache = None                               # the graph bakes pointers in: decide afresh what gets captured
         self._g_coords = torch.zeros(batch_size, 3, dtype=torch.float32, device=dev)
         self._g_gts = torch.zeros(batch_size, 1, dtype=torch.float32, device=dev)
+        self._g_rgb = torch.zeros(batch_size, 3, dtype=torch.float32, device=dev) if self.textured else None
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                          # warm-up off the default stream (allocator, lazy set-up)
             for _ in range(3):
-                self._forward_backward(self._g_coords, self._g_gts)
+                self._forward_backward(self._g_coords, self._g_gts, self._g_rgb)
         torch.cuda.current_stream().wait_stream(side)
         self.flat.grad.zero_()                                 # the warm-up passes accumulated gradients; parameters untouched
         graph = torch.cuda.CUDAGraph()
         # (captured on the warm-up stream: the per-(device, stream) scratch the ops keep was created - and zeroed - there; on another
         #  stream they would allocate it anew INSIDE the capture, and every replay would zero a few MB again)
         with torch.cuda.graph(graph, stream=side):
-            self._g_loss = self._forward_backward(self._g_coords, self._g_gts)
+            self._g_loss = self._forward_backward(self._g_coords, self._g_gts, self._g_rgb)
+            self._g_l2, self._g_rgbsum = self.last_l2, self.last_rgb
         self.flat.grad.zero_()
         self._graph = graph
         return self
 
     def static_inputs(self):
-        """(coords [B,3], gts [B,1]) buffers of the captured graph, or None: a loader that fills THESE and hands them to step()
-        spares the two device copies step() otherwise makes into them."""
+        """(coords [B,3], gts [B,1]) buffers of the captured graph - for a textured field (coords, gts, rgb [B,3]) - or None: a
+        loader that fills THESE and hands them to step() spares the device copies step() otherwise makes into them."""
         if getattr(self, "_graph", None) is None:
             return None
+        if self.textured:
+            return self._g_coords, self._g_gts, self._g_rgb
         return self._g_coords, self._g_gts
 
-    def step(self, coords, gts):
-        """coords [B,3], gts [B,1] on the GPU -> loss tensor (already divided by the batch size, like the reference)."""
+    def step(self, coords, gts, rgb=None):
+        """coords [B,3], gts [B,1] on the GPU -> loss tensor (already divided by the batch size, like the reference).  A textured
+        field (NeuralSDFTex) also needs rgb [B,3+]; afterwards last_l2 / last_rgb hold the two un-normalised sums the
+        reference's tracker adds up, as device tensors."""
+        if self.textured and rgb is None:
+            raise ValueError("SDFTrainStep.step: `rgb` is required for a field that predicts 'rgb' and 'sdf' together")
+        if not self.textured and rgb is not None:
+            raise ValueError("SDFTrainStep.step: `rgb` was given, but this field has no colour output to fit it with")
         graph = getattr(self, "_graph", None)
-        if graph is not None and tuple(coords.shape) == tuple(self._g_coords.shape) and tuple(gts.shape) == tuple(self._g_gts.shape):
+        if graph is not None and tuple(coords.shape) == tuple(self._g_coords.shape) and tuple(gts.shape) == tuple(self._g_gts.shape) \
+                and (rgb is None or tuple(rgb.shape) == tuple(self._g_rgb.shape)):
             if coords is not self._g_coords:
                 self._g_coords.copy_(coords)
             if gts is not self._g_gts:
                 self._g_gts.copy_(gts)
+            if rgb is not None and rgb is not self._g_rgb:
+                self._g_rgb.copy_(rgb)
             graph.replay()
             self.optimizer_step()
+            if self.textured:
+                self.last_l2, self.last_rgb = self._g_l2.clone(), self._g_rgbsum.clone()
             return self._g_loss.clone()
-        loss = self._forward_backward(coords, gts)
+        loss = self._forward_backward(coords, gts, rgb)
         self.optimizer_step()
         return loss
 

@@ -3,11 +3,14 @@ and this package's classes - OctreeAS.from_mesh(sample_tex=True), OctreeGrid, Ne
 wisp.ops.mesh.closest_tex, SDFTrainer (Adam, resampling every epoch).  Then one view is sphere-traced with PackedSDFTracer and
 the colour of the field at the hits, nef(coords=rb.xyz[rb.hit], channels="rgb"), is written to albedo.png.
 
-    python scripts/train_sdf_tex.py OBJ [--epochs N] [--dataset octree|mesh] [--out-dir DIR]
+    python scripts/train_sdf_tex.py OBJ [--epochs N] [--dataset octree|mesh] [--fused-step] [--out-dir DIR]
     python scripts/train_sdf_tex.py --write-test-mesh DIR ...
 
 --write-test-mesh DIR first writes a procedural textured torus (torus.obj + torus.mtl + stripes.png + checker.png: three materials -
 a striped RGB map, a plain diffuse colour, a checker RGBA map) into DIR and then fits it, so the script runs where no asset exists.
+--fused-step trains with SDFTrainStep (flat parameter buffer, single-launch optimizer, forward + loss + backward of a batch as the
+fused four-launch step, replayed as a HIP graph for whole batches) instead of SDFTrainer's torch.optim loop: same batches per epoch,
+same resampling, the same two per-sample means.
 The last line printed is one JSON record: losses of the first and the last epoch, hit count, seconds."""
 import argparse
 import json
@@ -104,6 +107,31 @@ def render_albedo(nef, h, w, device, num_steps=64):
     return (img.clamp(0, 1) * 255).round().to(torch.uint8).reshape(h, w, 3).cpu().numpy(), int(hit.sum())
 
 
+def fit_fused(nef, ds, cfg, device, epochs):
+    """SDFTrainer's epochs with SDFTrainStep: shuffled batches of cfg.dataloader.batch_size (the last one may be short and is
+    issued eagerly), the two un-normalised sums added up on the device and read back once per epoch, resampling after it."""
+    from wisp.trainers import SDFTrainStep
+    oc, bs = cfg.optimizer, cfg.dataloader.batch_size
+    step = SDFTrainStep(nef, lr=oc.lr, eps=oc.eps, grid_lr_weight=cfg.grid_lr_weight, betas=oc.betas, optimizer='adam',
+                        only_last=cfg.only_last)
+    if torch.device(device).type == 'cuda' and len(ds) >= bs:
+        step.capture(bs)
+    nef.train()
+    for epoch in range(cfg.max_epochs):
+        coords, sdf, rgb = (ds.data[k].to(device) for k in ("coords", "sdf", "rgb"))
+        order = torch.randperm(coords.shape[0], device=coords.device)
+        l2, col = torch.zeros((), device=coords.device), torch.zeros((), device=coords.device)
+        for a in range(0, order.shape[0], bs):
+            pick = order[a:a + bs]
+            step.step(coords[pick], sdf[pick].reshape(-1, 1), rgb[pick][..., :3].contiguous())
+            l2, col = l2 + step.last_l2, col + step.last_rgb
+        epochs.append((float(l2) / order.shape[0], float(col) / order.shape[0]))
+        logging.info('EPOCH {}/{} | l2 loss: {:>.3E} | rgb loss: {:>.3E}'.format(epoch + 1, cfg.max_epochs, *epochs[-1]))
+        if cfg.resample:
+            ds.resample()
+    nef.eval()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("obj", nargs="?")
@@ -114,6 +142,7 @@ def main(argv=None):
     ap.add_argument("--num-samples", type=int, default=100000)
     ap.add_argument("--mesh-samples", type=int, default=2_000_000, help="surface samples the occupancy octree is built from")
     ap.add_argument("--batch-size", type=int, default=512)
+    ap.add_argument("--fused-step", action="store_true")
     ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"))
     ap.add_argument("--out-dir", default=os.path.join("_results", "sdf-tex"))
     ap.add_argument("--device", default="cuda")
@@ -140,9 +169,12 @@ def main(argv=None):
             m = self.tracker.metrics
             epochs.append((m.average_metric('l2_loss'), m.average_metric('rgb_loss')))
 
-    trainer = Trainer(cfg, pipeline, ds, device=args.device)
     t0 = time.time()
-    trainer.train()
+    if args.fused_step:
+        fit_fused(pipeline.nef, ds, cfg, args.device, epochs)
+    else:
+        trainer = Trainer(cfg, pipeline, ds, device=args.device)
+        trainer.train()
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     seconds = time.time() - t0
