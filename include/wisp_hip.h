@@ -38,7 +38,7 @@ const char* wisp_last_error(void);
  * slot scales of the hash-grid backward; 4 = round 4: workspace + row counts of the order-free trilinear / codebook backward.
  * Entry points that are only ADDED - wisp_spc_query_chain, wisp_composite_loss, wisp_codebook_trilinear_multi_bwd,
  * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
- * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step - do not bump it). */
+ * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -474,6 +474,30 @@ int wisp_sdf_trace_step_fused(int64_t num_packs, int first, const float* nug_o, 
                               const int32_t* trinkets, const void* const* feats, int feats_dtype, const int32_t* levels,
                               int num_lods, int channels, int half_round, const float* w1, const float* b1, const float* w2,
                               const float* b2, int hidden, float scale, int32_t* any_active, wisp_stream_t stream);
+
+/* Evaluation of an nglod field at arbitrary points, one launch (csrc/sdf_eval.hip): what NeuralSDF.sdf / NeuralSDFTex.rgbsdf
+ * compute over the grid ops (wisp/models/nefs/neural_sdf.py:120-155, neural_sdf_tex.py:85-123) for the field shape of
+ * wisp_sdf_trace_step_fused - 16 'sum'-med OctreeGrid channels, input [position, features], one hidden relu layer of width
+ * <= 256 - with the octree walked inside the kernel (no pidx): a point outside [-1,1]^3 or in an unoccupied cell gets zero
+ * features and the decoder still runs.  coords f32 [n,3] -> out f32 [n, out_rows], out_rows 1 or 4 (the decoder's raw outputs
+ * in module order; the distance is the last row); w1 [hidden, 19], b1 [hidden], w2 [out_rows, hidden], b2 [out_rows]; feats /
+ * levels: HOST arrays as for the fused march.  With gts f32 [n] and counts i64 [2] the launch also ADDS
+ * #(pred < 0 & gt < 0) to counts[0] and #(pred < 0 | gt < 0) to counts[1] - the two sums of compute_sdf_iou
+ * (wisp/ops/sdf/metrics.py:12-29; the validation loop wisp/trainers/sdf_trainer.py:156-190 reads them back per batch); out may
+ * then be NULL. */
+int wisp_sdf_query(const float* coords, int64_t n, const uint8_t* octree, const int32_t* exsum, const int16_t* points,
+                   const int32_t* trinkets, const void* const* feats, int feats_dtype, const int32_t* levels, int num_lods,
+                   int channels, int half_round, const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
+                   int out_rows, float* out, const float* gts, int64_t* counts, wisp_stream_t stream);
+
+/* Central-difference gradient of that field's distance row in one launch (replaces finitediff_gradient,
+ * wisp/ops/differential/gradients.py:29-45, as PackedSDFTracer calls it for normals, wisp/tracers/packed_sdf_tracer.py:160-166:
+ * six field queries): grad[i, a] = (f(x + eps e_a) - f(x - eps e_a)) / (2 eps), positions and difference in fp32, every value
+ * bit for bit what the query entry point returns at that position.  grad f32 [n,3]. */
+int wisp_sdf_fd_gradient(const float* coords, int64_t n, const uint8_t* octree, const int32_t* exsum, const int16_t* points,
+                         const int32_t* trinkets, const void* const* feats, int feats_dtype, const int32_t* levels, int num_lods,
+                         int channels, int half_round, const float* w1, const float* b1, const float* w2, const float* b2,
+                         int hidden, int out_rows, float eps, float* grad, wisp_stream_t stream);
 
 /* Compositing + photometric loss + compositing backward of a TRAINING step in one launch (what
  * wisp/tracers/packed_rf_tracer.py:143-165, wisp/trainers/multiview_trainer.py:140-154 and their autograd backward do in

@@ -76,6 +76,10 @@ SIGNATURES = {
     "wisp_sdf_trace_step_fused": [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                   c_vp, c_i32, c_f32, c_vp, c_vp],
+    "wisp_sdf_query": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                       c_vp, c_vp, c_vp, c_vp],
+    "wisp_sdf_fd_gradient": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                             c_i32, c_f32, c_vp, c_vp],
     "wisp_sdf_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32],
     "wisp_sdf_train_step": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
@@ -1308,6 +1312,51 @@ def sdf_trace_step_fused(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr
                                          _p(points), _p(trinkets), fp, _DTYPE_CODE[feats[0].dtype], lv, n, feats[0].shape[1],
                                          int(half_round), _p(w1), _p(b1), _p(w2), _p(b2), w1.shape[0], float(np.float32(scale)),
                                          _p(any_active), _stream()), "sdf_trace_step_fused")
+
+
+def _sdf_field_args(fld):
+    """the field part of the wisp_sdf_query / wisp_sdf_fd_gradient argument lists from a dict of wisp.ops.sdf.fused_sdf_field"""
+    feats = fld["feats"]
+    n = len(feats)
+    for f in feats:
+        assert f.is_cuda and f.is_contiguous() and f.dtype == feats[0].dtype and f.shape[1] == feats[0].shape[1]
+    w1, b1, w2, b2 = fld["w1"], fld["b1"], fld["w2"], fld["b2"]
+    rows = b2.numel()
+    for a in (w1, b1, w2, b2):
+        assert a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()
+    assert w1.shape[1] == 3 + feats[0].shape[1] and b1.numel() == w1.shape[0] and w2.numel() == rows * w1.shape[0]
+    fp = (ctypes.c_void_p * n)(*[f.data_ptr() for f in feats])
+    lv = (ctypes.c_int32 * n)(*[int(l) for l in fld["levels"]])
+    return (_p(_need(fld["octree"], torch.uint8, "octree")), _p(_need(fld["exsum"], torch.int32, "exsum")),
+            _p(_need(fld["points"], torch.int16, "points")), _p(_need(fld["trinkets"], torch.int32, "trinkets")), fp,
+            _DTYPE_CODE[feats[0].dtype], lv, n, feats[0].shape[1], int(bool(fld["half_round"])), _p(w1), _p(b1), _p(w2), _p(b2),
+            w1.shape[0], rows), (fp, lv)
+
+
+def sdf_query(coords, fld, gts=None, counts=None, with_out=True):
+    """Field values at coords [n,3] -> f32 [n, rows] (rows = 1, or 4 for a textured field: the decoder's raw outputs), one launch
+    (csrc/sdf_eval.hip).  gts [n] + counts (int64 [2], ADDED to): intersection / union of (pred < 0), (gt < 0) on the distance
+    row; with_out=False returns None and only counts."""
+    coords = _need(coords, torch.float32, "coords")
+    n = coords.shape[0]
+    args, keep = _sdf_field_args(fld)
+    out = torch.empty(n, args[-1], dtype=torch.float32, device=coords.device) if with_out else None
+    if counts is not None:
+        gts = _need(gts, torch.float32, "gts").reshape(-1)
+        assert gts.shape[0] == n and counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
+    _check(lib.wisp_sdf_query(_p(coords), n, *args, _p(out), _p(gts) if counts is not None else c_vp(0), _p(counts), _stream()),
+           "sdf_query")
+    return out
+
+
+def sdf_fd_gradient(coords, fld, eps=0.005):
+    """Central-difference gradient [n,3] of the field's distance row at coords [n,3], one launch (csrc/sdf_eval.hip)."""
+    coords = _need(coords, torch.float32, "coords")
+    n = coords.shape[0]
+    args, keep = _sdf_field_args(fld)
+    grad = torch.empty(n, 3, dtype=torch.float32, device=coords.device)
+    _check(lib.wisp_sdf_fd_gradient(_p(coords), n, *args, float(np.float32(eps)), _p(grad), _stream()), "sdf_fd_gradient")
+    return grad
 
 
 _sdf_scratch = _Scratch(zeroed=False)      # (SDFTrainStep.capture bakes its address into a HIP graph: _Scratch keeps it alive)

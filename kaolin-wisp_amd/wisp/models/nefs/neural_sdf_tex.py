@@ -1,7 +1,7 @@
 """NeuralSDFTex: octree feature grid (+ optional embedded position) -> MLP -> surface colour and signed distance, NGLOD with
 albedo.  Mirrors wisp/models/nefs/neural_sdf_tex.py:20-123: constructor schema and attributes, a BasicDecoder with four outputs,
 the forward function `rgbsdf` registered for the channels "rgb" and "sdf".  `rgbsdf` itself runs over the grid ops and autograd
-(there is no fused inference query: what existing calls return stays as it is).  Training and marching have fused paths for the
+(what existing calls return stays as it is; wisp.ops.sdf.sdf_query evaluates the same four outputs in one launch for that shape).  Training and marching have fused paths for the
 shape of nglod_octree.yaml - 16 'sum' OctreeGrid features, one hidden relu layer, embedder_type 'none' or the identity position:
 SDFTrainStep.step(coords, gts, rgb) runs forward + loss + backward as wisp_sdf_tex_train_step (four launches), and
 PackedSDFTracer marches on the decoder's fourth output row through wisp_sdf_trace_step_fused; any other shape takes the modular

@@ -44,3 +44,35 @@ def normalized_grid(height, width, jitter=False, device='cuda', use_aspect=True)
         lines[longer] = lines[longer] * ratio
     # every row repeats the x line, every column the y line
     return torch.stack([lines['x'][None, :].expand(height, width), lines['y'][:, None].expand(height, width)], dim=-1)
+
+
+def normalized_slice(height, width, dim=0, depth=0.0, device='cuda'):
+    """3D points of an axis-aligned cutting plane, [height, width, 3] (wisp/ops/geometric.py:102-127): the normalized window's
+    (x, y) fill the two axes other than `dim` in ascending order, `dim` holds `depth`, and the y AXIS OF SPACE is mirrored at the
+    end.  Like the reference it hands `device` to normalized_grid positionally, i.e. as its `jitter` flag: every device string
+    jitters the window by up to half a pixel and the window lands on normalized_grid's default device ('cuda'), while the
+    `depth` column is made on `device` - reproduced, because the reference's slices look the way they do through it."""
+    window = normalized_grid(height, width, device)
+    if dim not in (0, 1, 2):
+        raise ValueError("dim is invalid!")
+    plane = torch.ones(height, width, 1, device=device) * depth
+    parts = [window[..., 0:1], window[..., 1:2]]
+    parts.insert(dim, plane)
+    pts = torch.cat(parts, dim=-1)
+    pts[..., 1] *= -1
+    return pts
+
+
+def spherical_envmap(ray_dir, normal):
+    """Matcap (sphere-map) texture coordinates [N, 2] in [0, 1] from viewing directions and normals [..., 3]
+    (wisp/ops/geometric.py:130-155): reflect the screen-space direction (z flipped) about the normal, r = d - 2 (d . n) n, shift
+    z by -1, uv = 1 - (r_xy / (2 |r|) + 0.5), clipped; NaN (a zero-length r) becomes 0."""
+    d = ray_dir.clone()
+    d[..., 2] *= -1
+    r = d - 2.0 * torch.sum(normal * d, dim=-1, keepdim=True) * normal
+    r[..., 2] -= 1.0
+    m = 2.0 * torch.sqrt(torch.sum(r ** 2, dim=-1, keepdim=True))
+    uv = 1.0 - ((r[..., :2] / m) + 0.5)
+    uv = torch.clip(uv[..., :2].reshape(-1, 2), 0.0, 1.0)
+    uv[torch.isnan(uv)] = 0
+    return uv

@@ -175,7 +175,7 @@ class PackedSDFTracer(BaseTracer):
         if fld is not None:
             with torch.no_grad():
                 self._march_fused(fld, rays, rt.pidx, depth, st, num_steps, invres * step_size, min_dis * invres)
-            return self._gather(nef, rays, st, channels, extra_channels, lod_idx)
+            return self._gather(nef, rays, st, channels, extra_channels, lod_idx, bool(getattr(self, "fused_normals", False)))
         with torch.no_grad():
             self._query(nef, st, lod_idx, invres * step_size)
             st.dist_prev.copy_(st.dist)
@@ -185,11 +185,14 @@ class PackedSDFTracer(BaseTracer):
                 st.nug, st.nug_next = st.nug_next, st.nug
                 if not bool(self._query(nef, st, lod_idx, invres * step_size).any()):
                     break
-        return self._gather(nef, rays, st, channels, extra_channels, lod_idx)
+        return self._gather(nef, rays, st, channels, extra_channels, lod_idx, bool(getattr(self, "fused_normals", False)))
 
     @staticmethod
-    def _gather(nef, rays, st, channels, extra_channels, lod_idx):
-        """scatter the per-pack results into per-ray buffers (rays without nuggets keep zeros)."""
+    def _gather(nef, rays, st, channels, extra_channels, lod_idx, fused_normals=False):
+        """scatter the per-pack results into per-ray buffers (rays without nuggets keep zeros).  fused_normals (the tracer
+        attribute of that name, unset by default; OfflineRenderer.render sets it): the normals come from
+        wisp.ops.sdf.sdf_fd_gradient - one launch on an nglod-shaped field - instead of six field queries; at the finest LOD
+        either way, as the forward function of the unfused path is called without a lod_idx."""
         o = rays.origins
         dev = o.device
         hit = st.hit.bool()
@@ -207,7 +210,11 @@ class PackedSDFTracer(BaseTracer):
         out["depth"][on_surface] = st.t[hit][:, None]
         if "rgb" in channels or "normal" in channels:
             if bool(hit.any()):
-                grad = finitediff_gradient(st.x[hit], nef.get_forward_function("sdf"))
+                if fused_normals:
+                    from wisp.ops.sdf import sdf_fd_gradient
+                    grad = sdf_fd_gradient(nef, st.x[hit], None)
+                else:
+                    grad = finitediff_gradient(st.x[hit], nef.get_forward_function("sdf"))
                 out["normal"][on_surface] = F.normalize(grad, p=2, dim=-1, eps=1e-5)
             out["rgb"][..., :3] = (out["normal"] + 1.0) / 2.0
         out["alpha"][on_surface] = 1.0

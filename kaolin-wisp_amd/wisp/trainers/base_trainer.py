@@ -136,8 +136,12 @@ class _Tracker:
     def __init__(self, log_dir=None):
         self.metrics = _Metrics()
         self.log_dir = log_dir or os.path.join('_results', 'logs', 'runs')
+        self.visualizer = None             # an OfflineRenderer (wisp.trainers.tracker), set by whoever wants images
 
     def log_metric(self, *a, **k):
+        pass
+
+    def log_image(self, *a, **k):
         pass
 
     def log_artifact(self, *a, **k):

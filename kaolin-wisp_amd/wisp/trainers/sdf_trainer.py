@@ -292,6 +292,8 @@ class SDFTrainer(BaseTrainer):
 
     def post_epoch(self):
         super().post_epoch()
+        if self.cfg.log_2d and self.cfg.render_every > -1 and self.epoch % self.cfg.render_every == 0:
+            self.render_snapshot()
         if self.cfg.resample:
             self.resample_dataset()
 
@@ -329,8 +331,81 @@ class SDFTrainer(BaseTrainer):
         loss.backward()
         self.optimizer.step()
 
+    def _validation_metric_name(self):
+        from wisp.datasets import MeshSampledSDFDataset, OctreeSampledSDFDataset
+        if isinstance(self.train_dataset, MeshSampledSDFDataset):
+            return "volumetric_iou"
+        if isinstance(self.train_dataset, OctreeSampledSDFDataset):
+            return "narrowband_iou"
+        raise NotImplementedError
+
     def validate(self):
-        return None
+        """Intersection over union of the field's interior with the ground truth's over the TRAINING set (the field is fitted to
+        one shape), one score per loader batch and loss LOD, as wisp/trainers/sdf_trainer.py:156-190: metric name by dataset
+        class, `tracker.log_metric('Validation/<name>/<lod>', score, epoch)` for the pairs of zip(loss_lods, scores) - the
+        reference's loop, which logs only the first len(loss_lods) scores while its console line divides their sum by the
+        number of ALL scores; reproduced as it stands.  Added: returns {name: [mean score over all batches, per loss LOD]}
+        (the reference returns None).
+        On an nglod-shaped field (wisp.ops.sdf.fused_sdf_field) a batch is one wisp_sdf_query launch that adds its two counts
+        to its own row of a zeroed [batches x lods, 2] int64 tensor, read back once at the end; otherwise one field query and
+        compute_sdf_iou - with its two read-backs - per batch, as in the reference."""
+        from wisp.ops.sdf import compute_sdf_iou, fused_sdf_field
+        metric_name = self._validation_metric_name()
+        nef = self.pipeline.nef
+        loss_lods = getattr(self, "loss_lods", None)
+        if loss_lods is None:                             # (pre_epoch sets it; validate() before any epoch derives it the same way)
+            lods = list(range(nef.grid.num_lods))
+            loss_lods = lods[-1:] if self.cfg.only_last else lods
+        on_gpu = torch.device(self.device).type == 'cuda'
+        fields = {lod: (fused_sdf_field(nef, lod) if on_gpu else None) for lod in loss_lods}
+        rows = len(self.train_data_loader) * len(loss_lods)
+        counts = torch.zeros(rows, 2, dtype=torch.int64, device=self.device) if any(f is not None for f in fields.values()) else None
+        scores = []                                       # a float, or the row of `counts` that will give it
+        with torch.no_grad():
+            for data in self.train_data_loader:
+                pts = data['coords'].to(self.device)
+                gts = data['sdf'].to(self.device)
+                for lod_idx in loss_lods:
+                    fld, row = fields[lod_idx], len(scores)
+                    if fld is not None and row < rows and pts.shape[0] > 0:
+                        _hip().sdf_query(pts, fld, gts=gts, counts=counts[row], with_out=False)
+                        scores.append(row)
+                    else:
+                        pred = nef(coords=pts, lod_idx=lod_idx, channels="sdf")
+                        scores.append(float(compute_sdf_iou(pred, gts)))
+        if counts is not None:
+            host = counts.cpu().tolist()                  # the one read-back
+            scores = [s if isinstance(s, float) else 100.0 * (float(host[s][0]) / float(host[s][1])) for s in scores]
+        val_dict = {metric_name: scores}
+        log_text = 'EPOCH {}/{}'.format(self.epoch, self.max_epochs)
+        for k, v in val_dict.items():
+            score_total = 0.0
+            for lod, score in zip(loss_lods, v):
+                self.tracker.log_metric(f'Validation/{k}/{lod}', score, self.epoch)
+                score_total += score
+            log_text += ' | {}: {:.4f}'.format(k, score_total / len(v))
+        log.info(log_text)
+        n = len(loss_lods)
+        return {metric_name: [sum(scores[i::n]) / len(scores[i::n]) for i in range(n)] if scores else []}
+
+    def render_snapshot(self):
+        """The three axis-aligned cross-sections of the distance field through `tracker.visualizer.sdf_slice`, logged as images
+        when cfg.log_2d is set (wisp/trainers/sdf_trainer.py:138-154).  A tracker without a visualizer gets an OfflineRenderer."""
+        self.pipeline.eval()
+        if not self.cfg.log_2d:
+            return
+        from wisp.trainers.tracker import OfflineRenderer
+        renderer = getattr(self.tracker, 'visualizer', None)
+        if renderer is None:
+            renderer = self.tracker.visualizer = OfflineRenderer(device=self.device)
+        nef = self.pipeline.nef
+        d = nef.grid.num_lods - 1
+        # an OfflineRenderer of this package is handed the field itself and evaluates it through wisp.ops.sdf.sdf_query (one
+        # launch on an nglod-shaped field); any other visualizer gets the 'sdf' forward function, as the reference hands it
+        what = nef if isinstance(renderer, OfflineRenderer) else nef.get_forward_function("sdf")
+        for axis, name in enumerate("XYZ"):
+            img = torch.FloatTensor(renderer.sdf_slice(what, dim=axis))
+            self.tracker.log_image(f'Cross-section/{name}/{d}', img.permute(2, 0, 1), self.epoch)
 
     def log_console(self):
         m = self.tracker.metrics

@@ -1,0 +1,138 @@
+"""Fit a signed distance field to an OBJ and look at the result: the flow of app/nglod/main_nglod.py with this package's classes -
+OctreeAS.from_mesh, OctreeGrid, NeuralSDF, a mesh SDF dataset, SDFTrainer with its IoU validation - then an OfflineRenderer
+snapshot (render.png) and the three axis-aligned distance cross-sections (slice_x.png, slice_y.png, slice_z.png).
+
+    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--fused-step] [--out-dir DIR]
+    python scripts/train_nglod.py --write-test-mesh DIR ...
+
+--write-test-mesh DIR first writes the procedural torus of scripts/train_sdf_tex.py into DIR and fits that.
+--fused-step trains with SDFTrainStep (flat parameter buffer, single-launch optimizer, fused forward + loss + backward, replayed
+as a HIP graph for whole batches) instead of SDFTrainer's torch.optim loop; validation is SDFTrainer.validate either way.
+The last line printed is one JSON record with the IoU before and after training."""
+import argparse
+import json
+import logging
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd"), os.path.join(ROOT, "scripts")]
+
+
+def build(obj, device, level=6, dataset="octree", num_samples=100000, samples_per_voxel=16, num_lods=4, hidden_dim=128,
+          num_samples_on_mesh=2_000_000):
+    """(dataset, pipeline) as main_nglod.py builds them from nglod_octree.yaml."""
+    from wisp.accelstructs import OctreeAS
+    from wisp.datasets import MeshSampledSDFDataset, OctreeSampledSDFDataset
+    from wisp.models import Pipeline
+    from wisp.models.grids import OctreeGrid
+    from wisp.models.nefs import NeuralSDF
+    from wisp.tracers import PackedSDFTracer
+    blas = OctreeAS.from_mesh(obj, level=level, num_samples_on_mesh=num_samples_on_mesh)
+    if dataset == "octree":
+        ds = OctreeSampledSDFDataset(blas, split='train', num_samples=num_samples, samples_per_voxel=samples_per_voxel)
+    else:
+        ds = MeshSampledSDFDataset(obj, split='train', num_samples=max(num_samples // 5, 1))
+    grid = OctreeGrid(blas, feature_dim=16, num_lods=num_lods, multiscale_type='sum', feature_std=0.01)
+    nef = NeuralSDF(grid, pos_embedder='none', position_input=True, hidden_dim=hidden_dim, num_layers=1).to(device)
+    return ds, Pipeline(nef, PackedSDFTracer(num_steps=128, step_size=0.8, min_dis=0.0003))
+
+
+def fit_fused(trainer, ds, cfg, device):
+    """SDFTrainer's epochs with SDFTrainStep: shuffled batches of cfg.dataloader.batch_size, resampling after every epoch."""
+    from wisp.trainers import SDFTrainStep
+    oc, bs = cfg.optimizer, cfg.dataloader.batch_size
+    nef = trainer.pipeline.nef
+    step = SDFTrainStep(nef, lr=oc.lr, eps=oc.eps, grid_lr_weight=cfg.grid_lr_weight, betas=oc.betas, optimizer='adam',
+                        only_last=cfg.only_last)
+    if torch.device(device).type == 'cuda' and len(ds) >= bs:
+        step.capture(bs)
+    nef.train()
+    for epoch in range(cfg.max_epochs):
+        coords, sdf = ds.data["coords"].to(device), ds.data["sdf"].to(device)
+        order = torch.randperm(coords.shape[0], device=coords.device)
+        total = torch.zeros((), device=coords.device)
+        for a in range(0, order.shape[0], bs):
+            pick = order[a:a + bs]
+            total = total + step.step(coords[pick], sdf[pick].reshape(-1, 1)) * pick.shape[0]
+        logging.info('EPOCH {}/{} | l2 loss: {:>.3E}'.format(epoch + 1, cfg.max_epochs, float(total) / order.shape[0]))
+        if cfg.resample:
+            ds.resample()
+            trainer.init_dataloader()
+    nef.eval()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("obj", nargs="?")
+    ap.add_argument("--write-test-mesh", metavar="DIR")
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--dataset", choices=("octree", "mesh"), default="octree")
+    ap.add_argument("--level", type=int, default=6)
+    ap.add_argument("--num-lods", type=int, default=4)
+    ap.add_argument("--num-samples", type=int, default=100000)
+    ap.add_argument("--mesh-samples", type=int, default=2_000_000, help="surface samples the occupancy octree is built from")
+    ap.add_argument("--batch-size", type=int, default=512)
+    ap.add_argument("--fused-step", action="store_true")
+    ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("W", "H"))
+    ap.add_argument("--shading-mode", choices=("rb", "normal", "matcap"), default="normal")
+    ap.add_argument("--matcap-path", default=None)
+    ap.add_argument("--out-dir", default=os.path.join("_results", "nglod"))
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    from wisp.ops.image import save_u8
+    from wisp.trainers import ConfigAdam, ConfigDataloader, ConfigSDFTrainer, SDFTrainer
+    from wisp.trainers.tracker import OfflineRenderer
+    obj = args.obj
+    if args.write_test_mesh:
+        from train_sdf_tex import write_test_mesh
+        obj = write_test_mesh(args.write_test_mesh)
+    if not obj:
+        ap.error("give an OBJ or --write-test-mesh DIR")
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    ds, pipeline = build(obj, args.device, level=args.level, dataset=args.dataset, num_samples=args.num_samples,
+                         num_lods=args.num_lods, num_samples_on_mesh=args.mesh_samples)
+    cfg = ConfigSDFTrainer(optimizer=ConfigAdam(lr=1e-3, eps=1e-15), dataloader=ConfigDataloader(batch_size=args.batch_size),
+                           max_epochs=args.epochs, resample=True, only_last=True, exp_name='nglod', profile_nvtx=False,
+                           valid_every=-1)
+    trainer = SDFTrainer(cfg, pipeline, ds, device=args.device)
+    before = trainer.validate()
+    metric = next(iter(before))
+    t0 = time.time()
+    if args.fused_step:
+        fit_fused(trainer, ds, cfg, args.device)
+    else:
+        trainer.train()
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    seconds = time.time() - t0
+    pipeline.eval()
+    after = trainer.validate()
+    os.makedirs(args.out_dir, exist_ok=True)
+    renderer = OfflineRenderer(render_res=tuple(args.size), shading_mode=args.shading_mode,
+                               matcap_path=args.matcap_path or './data/matcap/Pearl.png', device=args.device)
+    rb = renderer.render_snapshot(pipeline, f=[1.4, 1.2, 1.6], t=[0, 0, 0], fov=40.0, camera_clamp=[0, 6])
+    shot = rb.transpose()                                   # back to [height, width, .]
+    img = torch.where(shot.hit.bool().reshape(*shot.rgb.shape[:2], 1), shot.rgb[..., :3], torch.ones_like(shot.rgb[..., :3]))
+    files = dict(render=os.path.join(args.out_dir, "render.png"))
+    save_u8(files["render"], (img.clamp(0, 1) * 255).round().to(torch.uint8).numpy())
+    for axis, name in enumerate("xyz"):
+        files[f"slice_{name}"] = os.path.join(args.out_dir, f"slice_{name}.png")
+        vis = renderer.sdf_slice(pipeline.nef, dim=axis)
+        save_u8(files[f"slice_{name}"], (np.clip(vis, 0, 1) * 255).round().astype(np.uint8).transpose(1, 0, 2))
+    rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
+               metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
+               seconds=round(seconds, 3), **{k: os.path.abspath(v) for k, v in files.items()})
+    print(json.dumps(rec))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

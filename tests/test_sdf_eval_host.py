@@ -1,0 +1,519 @@
+"""CPU: the host side of the nglod evaluation - the exactness conditions of tests/sdf_eval_ref.py's generator, the two entry
+points' declaration / binding / export and argument checks, wisp.ops.sdf / geometric / shaders, OfflineRenderer and
+SDFTrainer.validate against the reference's function and method bodies executed in place."""
+import ctypes
+import inspect
+import logging
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import kernel_meta
+import sdf_eval_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "kaolin-wisp_amd", "csrc", "libwisp_hip.so")
+REF = "/root/reference/wisp"
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
+
+
+# ------------------------------------------------------------------------------------------------ 1. the reference itself
+@pytest.mark.parametrize("hidden,rows,half,dtype", [(1, 1, False, torch.float32), (17, 4, True, torch.float32),
+                                                    (128, 1, True, torch.float16), (256, 4, False, torch.bfloat16)])
+def test_exact_query_cases_are_exact(hidden, rows, half, dtype):
+    """float64 and float32 evaluation agree bit for bit (the generator's own assertions ran when the case was built)"""
+    for levels in ((2, 3, 4), (2, 3)):
+        case = R.exact_case(levels, hidden, rows, n=400, seed=5, dtype=dtype, half_round=half)
+        a = R.reference(case["shell"], case["field"], case["coords"])
+        b = R.reference(case["shell"], case["field"], case["coords"], torch.float32)
+        assert torch.equal(a, b.double()) and a.shape == (400, rows)
+        chain = case["chain"]
+        assert int((chain[:, -1] < 0).sum()) > 40 and int(((chain[:, 0] >= 0) & (chain[:, -1] < 0)).sum()) > 5   # empty fine cell, live parent
+        assert bool((case["coords"].abs() > 1).any()) and bool((case["coords"] == 1.0).all(1).any())
+
+
+@pytest.mark.parametrize("hidden,rows", [(1, 1), (128, 4), (256, 1)])
+def test_exact_gradient_cases_are_exact(hidden, rows):
+    case = R.exact_gradient_case((2, 3, 4), hidden, rows, n=400, seed=6)
+    a = R.gradient_reference(case["shell"], case["field"], case["coords"], case["eps"])
+    b = R.gradient_reference(case["shell"], case["field"], case["coords"], case["eps"], torch.float32)
+    assert torch.equal(a, b.double()) and int((a != 0).sum()) > 200
+
+
+def test_an_inexact_case_is_refused():
+    sh = R.shell(4)
+    fld = R.exact_field(sh, (2, 3, 4), 128, 1, seed=1)
+    with pytest.raises(AssertionError):
+        R.check_exact(sh, fld, R.generic_points(50, seed=1), 1)
+
+
+def test_generic_iou_inputs_have_few_points_near_the_surface():
+    """the counts test allows intersection / union to move by the number of points whose |pred| lies below the fused-vs-modular
+    difference (~1e-6): on the CPU oracle that number, at a hundred times the difference, is under 1 % of the batch"""
+    sh = R.shell(4)
+    fld = R.generic_field(sh, (2, 3, 4), 128, 1, seed=3)
+    coords = R.generic_points(1000, seed=9)
+    pred = R.reference(sh, fld, coords)[:, -1]
+    pred = pred - pred.median()                            # (the GPU test moves the output bias the same way)
+    gts = R.sphere_sdf(coords).double()
+    assert int((pred.abs() < 1e-4).sum()) < 10
+    inter, union = int(((pred < 0) & (gts < 0)).sum()), int(((pred < 0) | (gts < 0)).sum())
+    assert 0 < inter < union < 1000
+
+
+# ------------------------------------------------------------------------------------------------ 2. ABI and argument checks
+def test_the_two_entry_points_are_declared_bound_and_exported():
+    import wisp._C as C
+    header = open(os.path.join(ROOT, "include", "wisp_hip.h")).read()
+    assert "int wisp_sdf_query(" in header and "int wisp_sdf_fd_gradient(" in header
+    assert "metrics.py:12-29" in header and "gradients.py:29-45" in header          # the reference lines they replace
+    assert len(C.SIGNATURES["wisp_sdf_query"]) == 22 and len(C.SIGNATURES["wisp_sdf_fd_gradient"]) == 21
+    lib = ctypes.CDLL(C.LIB_PATH)
+    assert hasattr(lib, "wisp_sdf_query") and hasattr(lib, "wisp_sdf_fd_gradient")
+    assert C.lib.wisp_abi_version() == 4 == C.ABI_VERSION
+    assert callable(C.sdf_query) and callable(C.sdf_fd_gradient)
+    mk = open(os.path.join(ROOT, "kaolin-wisp_amd", "csrc", "Makefile")).read()
+    assert "sdf_eval.hip" in mk and "sdf_eval_dev.h" in mk
+
+
+def _host_args(gradient=False, levels=(2, 3, 4)):
+    """a call whose sizes are valid and whose pointers point at host memory: nothing may be dereferenced on the way to a refusal
+    (the level list and the table pointer array are host arrays by contract)"""
+    buf = ctypes.create_string_buffer(4096)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    n = len(levels)
+    feats = (ctypes.c_void_p * max(n, 1))(*[ptr.value] * n)
+    lv = (ctypes.c_int32 * max(n, 1))(*levels)
+    #        coords n octree exsum points trinkets feats dtype levels lods C half w1 b1 w2 b2 hidden rows
+    args = [ptr, 8, ptr, ptr, ptr, ptr, feats, 0, lv, n, 16, 0, ptr, ptr, ptr, ptr, 128, 1]
+    args += [ctypes.c_float(0.005), ptr, ctypes.c_void_p(0)] if gradient else [ptr, ptr, ptr, ctypes.c_void_p(0)]
+    return args, (buf, feats, lv)
+
+
+COORDS, N, OCTREE, FEATS, DTYPE, LEVELS, LODS, CHANNELS, W1, HIDDEN, ROWS, OUT, GTS, COUNTS = 0, 1, 2, 6, 7, 8, 9, 10, 12, 16, 17, 18, 19, 20
+
+
+@pytest.mark.parametrize("gradient", [False, True])
+def test_argument_checks_are_returned_before_any_launch(gradient):
+    import wisp._C as C
+    f = C._cdll.wisp_sdf_fd_gradient if gradient else C._cdll.wisp_sdf_query
+    null = ctypes.c_void_p(0)
+    bad = [{CHANNELS: 8}, {CHANNELS: 32}, {HIDDEN: 0}, {HIDDEN: 257}, {ROWS: 0}, {ROWS: 2}, {ROWS: 5}, {LODS: 0}, {LODS: 17},
+           {DTYPE: 3}, {N: -1}, {COORDS: null}, {OCTREE: null}, {W1: null}, {FEATS: null}, {LEVELS: null}]
+    if gradient:
+        bad += [{18: ctypes.c_float(0.0)}, {19: null}]                             # eps, grad
+    else:
+        bad += [{GTS: null}, {OUT: null, COUNTS: null}]                            # counts without gts; nothing to write
+    for patch in bad:
+        args, keep = _host_args(gradient)
+        for k, v in patch.items():
+            args[k] = v
+        assert f(*args) == -1, patch                                               # WISP_ERR_INVALID
+        assert C.lib.wisp_last_error()
+    for levels in ((2, 2, 4), (3, 2, 4), (2, 3, 16), (-1, 3, 4)):                   # not ascending / out of range
+        args, keep = _host_args(gradient, levels)
+        assert f(*args) == -1, levels
+    args, keep = _host_args(gradient)
+    args[FEATS][1] = None                                                          # a null table pointer inside the array
+    assert f(*args) == -1
+    # an empty batch is fine, with nothing but the field described
+    args, keep = _host_args(gradient)
+    args[N], args[COORDS] = 0, null
+    args[18 if not gradient else 19] = null
+    assert f(*args) == 0
+    args, keep = _host_args(gradient)
+    args[N], args[CHANNELS] = 0, 8                                                 # ... but the shape checks still come first
+    assert f(*args) == -1
+
+
+@pytest.mark.skipif(not kernel_meta.available(LIB), reason="libwisp_hip.so not built or llvm-readelf missing")
+def test_the_kernels_have_no_scratch():
+    meta = kernel_meta.kernels(LIB)
+    names = kernel_meta.demangled(list(meta))
+    kern = {names[k]: v for k, v in meta.items()}
+    for part in ("sdf_query_kernel<", "sdf_fd_gradient_kernel<"):
+        hits = {n: v for n, v in kern.items() if part in n}
+        assert len(hits) == 6, (part, list(hits))                                   # f32 / f16 / bf16 tables x 1 / 4 output rows
+        for name, v in hits.items():
+            assert v["scratch"] == 0 and v["wg"] == 256 and v["vgpr"] <= 96 and v["lds"] == 0, (name, v)
+
+
+# ------------------------------------------------------------------------------------------------ 3. wisp.ops.sdf on the host
+class _CudaLike(torch.Tensor):
+    is_cuda = True
+
+
+def _cpu_field(tex=False, pos=True, hidden=32, lods=3, feature_dim=16, multiscale='sum', positional=False, layers=1):
+    from wisp.accelstructs import OctreeAS
+    from wisp.models.grids import OctreeGrid
+    from wisp.models.nefs import NeuralSDF
+    from wisp.models.nefs.neural_sdf_tex import NeuralSDFTex
+    grid = OctreeGrid(OctreeAS.make_dense(3), feature_dim=feature_dim, num_lods=lods, multiscale_type=multiscale, feature_std=0.05)
+    if tex:
+        nef = NeuralSDFTex(grid, embedder_type=('positional' if positional else 'identity') if pos else 'none', hidden_dim=hidden,
+                           num_layers=layers)
+    else:
+        nef = NeuralSDF(grid, pos_embedder='positional' if positional else 'none', position_input=pos, hidden_dim=hidden,
+                        num_layers=layers)
+    # the shape rules ask for tables on the GPU: stand-ins that say so (nothing is launched here)
+    tables = [f.detach().as_subclass(_CudaLike) for f in grid.features]
+    del grid._modules["features"]
+    grid.features = tables
+    return nef
+
+
+def test_fused_sdf_field_accepts_the_nglod_shape_and_nothing_else(monkeypatch):
+    from wisp.ops.sdf import fused_sdf_field
+    ok = fused_sdf_field(_cpu_field(), 2)
+    assert ok is not None and ok["w2"].shape == (32,) and ok["b2"].shape == (1,) and ok["levels"] == [1, 2, 3] and len(ok["feats"]) == 3
+    assert fused_sdf_field(_cpu_field(), None)["levels"] == [1, 2, 3] and fused_sdf_field(_cpu_field(), 1)["levels"] == [1, 2]
+    tex = fused_sdf_field(_cpu_field(tex=True), 2)
+    assert tex["w2"].shape == (4, 32) and tex["b2"].shape == (4,) and tex["w1"].shape == (32, 19)
+    nopos = _cpu_field(tex=True, pos=False)
+    f = fused_sdf_field(nopos, 2)
+    assert f["w1"].shape == (32, 19) and bool((f["w1"][:, :3] == 0).all()) and torch.equal(f["w1"][:, 3:], nopos.decoder.layers[0].weight)
+    assert torch.equal(f["w2"], nopos.decoder.lout.weight) and torch.equal(f["b2"], nopos.decoder.lout.bias)
+    for name, nef, lod in (("lod 0", _cpu_field(), 0), ("cat", _cpu_field(multiscale='cat'), 2), ("8 channels", _cpu_field(feature_dim=8), 2),
+                           ("hidden 300", _cpu_field(hidden=300), 2), ("two layers", _cpu_field(layers=2), 2),
+                           ("fourier", _cpu_field(positional=True), 2), ("no position", _cpu_field(pos=False), 2),
+                           ("tex fourier", _cpu_field(tex=True, positional=True), 2), ("tex two layers", _cpu_field(tex=True, layers=2), 2)):
+        assert fused_sdf_field(nef, lod) is None, name
+    cpu = _cpu_field()
+    cpu.grid.features = [torch.Tensor(f) for f in cpu.grid.features]                # tables on the host
+    assert fused_sdf_field(cpu, 2) is None
+    assert fused_sdf_field(types.SimpleNamespace(grid=None), 2) is None
+    monkeypatch.setenv("WISP_SDF_FUSED", "0")
+    assert fused_sdf_field(_cpu_field(), 2) is None
+
+
+def test_sdf_query_and_gradient_fall_back_on_the_host():
+    from wisp.ops.differential import finitediff_gradient
+    from wisp.ops.sdf import sdf_query, sdf_fd_gradient, sdf_iou_counts, compute_sdf_iou
+
+    class Field:
+        grid = None
+        _forward_functions = {}
+
+        def __call__(self, coords=None, lod_idx=None, channels=None):
+            return (coords ** 2).sum(-1, keepdim=True) - 0.3 + 0.01 * (lod_idx or 0)
+    nef = Field()
+    x = torch.rand(50, 3) * 2 - 1
+    assert torch.equal(sdf_query(nef, x, 2), nef(coords=x, lod_idx=2))
+    assert torch.equal(sdf_fd_gradient(nef, x, 2), finitediff_gradient(x, lambda c: nef(coords=c, lod_idx=2)))
+    gts = x.norm(dim=1) - 0.5
+    counts = torch.zeros(2, dtype=torch.int64)
+    pred = sdf_query(nef, x, 1, gts=gts, counts=counts)
+    assert counts.tolist() == sdf_iou_counts(pred[:, 0], gts).tolist() and counts[1] > 0
+    assert compute_sdf_iou(pred, gts[:, None]) == 100.0 * (int(counts[0]) / int(counts[1]))
+    with pytest.raises(ValueError):
+        sdf_query(nef, x, 1, gts=gts)
+
+
+# ------------------------------------------------------------------------------------------------ 4. against the reference
+def _ref_fn(rel, name, glb):
+    from test_reference_modules import _reference_function
+    return _reference_function(rel, name, glb)
+
+
+@needs_ref
+def test_compute_sdf_iou_equals_the_reference_function():
+    from wisp.ops.sdf import compute_sdf_iou
+    ref = _ref_fn("ops/sdf/metrics.py", "compute_sdf_iou", dict(torch=torch))
+    g = torch.Generator().manual_seed(0)
+    for n in (1, 7, 512, 5000):
+        pred, gts = torch.randn(n, 1, generator=g), torch.randn(n, 1, generator=g) - 0.2
+        pred[0], gts[0] = -1.0, -1.0
+        assert compute_sdf_iou(pred, gts) == ref(pred, gts)
+    with pytest.raises(ZeroDivisionError):
+        compute_sdf_iou(torch.ones(4, 1), torch.ones(4, 1))
+    with pytest.raises(ZeroDivisionError):
+        ref(torch.ones(4, 1), torch.ones(4, 1))
+    import wisp.ops.sdf as S
+    assert not hasattr(S, "compute_sparse_sdf_iou")
+
+
+def _cpu_grid(height, width, jitter=False, device='cpu', use_aspect=True):
+    import wisp.ops.geometric as G
+    return G.normalized_grid(height, width, jitter, 'cpu', use_aspect)
+
+
+@needs_ref
+def test_geometric_helpers_equal_the_reference_functions(monkeypatch):
+    import wisp.ops.geometric as G
+    ref_slice = _ref_fn("ops/geometric.py", "normalized_slice", dict(torch=torch, normalized_grid=_cpu_grid))
+    ref_env = _ref_fn("ops/geometric.py", "spherical_envmap", dict(torch=torch))
+    real = G.normalized_grid
+    monkeypatch.setattr(G, "normalized_grid", lambda h, w, jitter=False, device='cpu', use_aspect=True: real(h, w, jitter, 'cpu', use_aspect))
+    for (h, w), dim, depth in (((8, 8), 0, 0.0), ((6, 10), 1, 0.25), ((9, 5), 2, -0.5)):
+        torch.manual_seed(3)                                # the device string lands on the `jitter` flag (see normalized_slice)
+        want = ref_slice(h, w, dim=dim, depth=depth, device='cpu')
+        torch.manual_seed(3)
+        got = G.normalized_slice(h, w, dim=dim, depth=depth, device='cpu')
+        assert got.shape == (h, w, 3) and torch.equal(got, want), (h, w, dim)
+        assert not torch.equal(got[..., (dim + 1) % 3], G.normalized_slice(h, w, dim=dim, depth=depth, device='cpu')[..., (dim + 1) % 3])
+    with pytest.raises(ValueError):
+        G.normalized_slice(4, 4, dim=3, device='cpu')
+    g = torch.Generator().manual_seed(1)
+    d = torch.nn.functional.normalize(torch.randn(6, 7, 3, generator=g), dim=-1)
+    n = torch.nn.functional.normalize(torch.randn(6, 7, 3, generator=g), dim=-1)
+    n[0, 0] = 0.0
+    d[0, 1], n[0, 1] = torch.tensor([0.0, 0.0, -1.0]), torch.tensor([0.0, 0.0, 1.0])       # r = 0: the NaN branch
+    d0, n0 = d.clone(), n.clone()
+    assert torch.equal(G.spherical_envmap(d, n), ref_env(d0.clone(), n0.clone()))
+    assert torch.equal(d, d0) and torch.equal(n, n0) and G.spherical_envmap(d, n).shape == (42, 2)
+
+
+@needs_ref
+def test_look_at_and_slice_colours_equal_the_reference():
+    import torch.nn.functional as F
+    import wisp.trainers.tracker.offline_renderer as mine
+    glb = dict(torch=torch, F=F, np=np, normalized_grid=_cpu_grid)
+    glb["_generate_rays"] = _ref_fn("trainers/tracker/offline_renderer.py", "_generate_rays", glb)
+    ref_look = _ref_fn("trainers/tracker/offline_renderer.py", "_look_at", glb)
+    for f, t, hw, mode, fov in (([0, 0, 1], [0, 0, 0], (6, 6), 'persp', 30.0), ([1.5, 0.7, -2.0], [0.1, 0.2, 0.0], (5, 9), 'persp', 70.0),
+                                ([1.0, 2.0, 3.0], [0, 0, 0], (7, 4), 'ortho', 45.0)):
+        o, d = mine._look_at(f, t, hw[0], hw[1], mode=mode, fov=fov, device='cpu')
+        ro, rd = ref_look([float(v) for v in f], [float(v) for v in t], hw[0], hw[1], mode=mode, fov=fov, device='cpu')
+        assert o.shape == (hw[0] * hw[1], 3) and torch.equal(o, ro) and torch.equal(d, rd), (f, mode)
+    with pytest.raises(ValueError):
+        mine._look_at([0, 0, 1], [0, 0, 0], 4, 4, mode='fisheye', device='cpu')
+    # the colour map: the reference's sdf_slice over a known distance function
+    from test_reference_modules import _reference_method
+    pts = torch.stack(torch.meshgrid(torch.linspace(-1, 1, 40), torch.linspace(-1, 1, 30), indexing='ij'), -1)
+    pts = torch.cat([pts, torch.zeros(40, 30, 1)], -1)
+    ref_slice = _reference_method("trainers/tracker/offline_renderer.py", "OfflineRenderer", "sdf_slice",
+                                  dict(torch=torch, np=np, normalized_slice=lambda *a, **k: pts))
+    me = types.SimpleNamespace(width=40, height=30, device='cpu')
+    fn = lambda x: x.norm(dim=1, keepdim=True) * 1.3 - 0.6                          # noqa: E731
+    want = ref_slice(me, fn, dim=2)
+    got = mine.sdf_slice_colors(fn(pts.reshape(-1, 3)).reshape(40, 30, 1).squeeze().numpy())
+    assert got.shape == (40, 30, 3) and np.array_equal(got, want)
+    assert (got == 0.8).all(-1).any() and (got == 0.0).all(-1).any() and (got == np.array([1.0, 0.38, 0.0])).all(-1).any()
+
+
+@needs_ref
+def test_offline_renderer_constructor_schema_equals_the_reference():
+    import ast
+    from wisp.trainers.tracker import OfflineRenderer
+    path = os.path.join(REF, "trainers/tracker/offline_renderer.py")
+    cls = next(n for n in ast.parse(open(path).read()).body if isinstance(n, ast.ClassDef) and n.name == "OfflineRenderer")
+    init = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "__init__")
+    names = [a.arg for a in init.args.args]
+    defaults = [ast.literal_eval(d) for d in init.args.defaults]
+    sig = inspect.signature(OfflineRenderer.__init__)
+    assert list(sig.parameters) == names
+    assert [p.default for p in list(sig.parameters.values())[1:]] == defaults
+    for meth in ("render_lookat", "render", "normal_slice", "sdf_slice", "render_snapshot"):
+        fn = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == meth)
+        assert list(inspect.signature(getattr(OfflineRenderer, meth)).parameters) == [a.arg for a in fn.args.args], meth
+        want = [ast.literal_eval(d) for d in fn.args.defaults]
+        got = [p.default for p in inspect.signature(getattr(OfflineRenderer, meth)).parameters.values() if p.default is not inspect._empty]
+        assert got == want, meth
+    r = OfflineRenderer(render_res=(64, 48), render_batch=100, shading_mode='normal', matcap_path='m.png', perf=True, device='cpu')
+    assert (r.width, r.height, r.render_res, r.render_batch, r.shading_mode, r.matcap_path, r.shadow, r.ao, r.perf, r.device) == \
+        (64, 48, (64, 48), 100, 'normal', 'm.png', False, False, True, 'cpu')
+
+
+def test_shadow_and_ambient_occlusion_are_refused():
+    from wisp.trainers.tracker import OfflineRenderer
+    with pytest.raises(NotImplementedError):
+        OfflineRenderer(shadow=True)
+    with pytest.raises(NotImplementedError):
+        OfflineRenderer(ao=True)
+    import wisp.ops.shaders as S
+    assert not hasattr(S, "pointlight_shadow_shader")
+
+
+# ------------------------------------------------------------------------------------------------ 5. matcap
+def test_matcap_lookup_equals_the_scipy_interpolator(tmp_path):
+    """The device lookup (bilinear over linspace(0, 1) knots of the transposed image) against the reference's
+    RegularGridInterpolator on a non-square 64 x 48 map.  Bound 1e-4 on [0, 1] colours: the fp32 texel coordinate is off by
+    ~2^-24 x width texels, times at most 255 levels per texel, / 255 - 6e-5 for maps up to 1024 wide."""
+    from scipy.interpolate import RegularGridInterpolator
+    from PIL import Image
+    from wisp.core import Rays, RenderBuffer
+    from wisp.ops.geometric import spherical_envmap
+    from wisp.ops.shaders import matcap_shader
+    from wisp.ops.shaders.matcap import matcap_sampler, matcap_lookup
+    rng = np.random.default_rng(0)
+    img = rng.integers(0, 256, size=(48, 64, 3), dtype=np.uint8)                   # height 48, width 64
+    img[::7] = 255
+    img[:, ::9] = 0
+    path = str(tmp_path / "matcap.png")
+    Image.fromarray(img).save(path)
+    t = np.array(Image.open(path)).transpose(1, 0, 2)
+    interp = RegularGridInterpolator((np.linspace(0, 1, t.shape[0]), np.linspace(0, 1, t.shape[1])), t)
+    uv = torch.from_numpy(rng.uniform(0, 1, size=(4000, 2)).astype(np.float32))
+    uv[:4] = torch.tensor([[0.0, 0.0], [1.0, 1.0], [0.0, 1.0], [1.0, 0.0]])
+    uv[4:67, 0], uv[4:67, 1] = torch.linspace(0, 1, 64)[:63], 0.5                  # on the knots of the long axis
+    tex = matcap_sampler(path)
+    assert tex.shape == (1, 3, 64, 48)
+    got = matcap_lookup(tex, uv) / 255.0
+    want = interp(uv.numpy().astype(np.float64)) / 255.0
+    err = float(np.abs(got.double().numpy() - want).max())
+    assert err <= 1e-4, err
+    # the shader end to end, with a model matrix
+    g = torch.Generator().manual_seed(2)
+    normal = torch.nn.functional.normalize(torch.randn(10, 12, 3, generator=g), dim=-1)
+    dirs = torch.nn.functional.normalize(torch.randn(10, 12, 3, generator=g), dim=-1)
+    mm = torch.linalg.qr(torch.randn(3, 3, generator=g))[0]
+    rb = matcap_shader(RenderBuffer(normal=normal.clone()), Rays(origins=torch.zeros(10, 12, 3), dirs=dirs.clone()), path, mm=mm)
+    view = torch.mm(dirs.reshape(-1, 3), mm.T).reshape(10, 12, 3)
+    vn = spherical_envmap(view, normal).numpy()
+    want = (interp(vn.astype(np.float64))[..., :3] / 255.0).reshape(10, 12, 3)
+    assert rb.rgb.shape == (10, 12, 3) and float(np.abs(rb.rgb.double().numpy() - want).max()) <= 1e-4
+    with pytest.raises(Exception, match="does not exist"):
+        matcap_shader(RenderBuffer(normal=normal), Rays(origins=dirs, dirs=dirs), str(tmp_path / "missing.png"))
+
+
+# ------------------------------------------------------------------------------------------------ 6. validation
+class _StubField(torch.nn.Module):
+    """CPU field: distance to a sphere whose radius depends on the LOD"""
+    def __init__(self):
+        super().__init__()
+        self.grid = types.SimpleNamespace(num_lods=3)
+        self.w = torch.nn.Parameter(torch.zeros(1))
+
+    def forward(self, coords=None, lod_idx=None, channels=None):
+        return coords.norm(dim=-1, keepdim=True) - (0.45 + 0.05 * lod_idx)
+
+
+class _Loader:
+    def __init__(self, batches):
+        self.batches = batches
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
+@needs_ref
+@pytest.mark.parametrize("only_last", [True, False])
+@pytest.mark.parametrize("dataset", ["mesh", "octree", "other"])
+def test_validate_equals_the_reference_method(only_last, dataset, caplog):
+    """SDFTrainer.validate (trainers/sdf_trainer.py:156-190), the method body compiled from the reference file, next to this
+    package's over the same stub trainer: the same log_metric calls - including the zip(loss_lods, scores) truncation - and the
+    same console line; four batches, the last one short"""
+    from test_reference_modules import _reference_method
+    from wisp.datasets import MeshSampledSDFDataset, OctreeSampledSDFDataset
+    from wisp.ops.sdf import compute_sdf_iou
+    from wisp.trainers import SDFTrainer
+    ref_log = logging.getLogger("reference_validate")
+    ref_validate = _reference_method("trainers/sdf_trainer.py", "SDFTrainer", "validate",
+                                     dict(torch=torch, log=ref_log, compute_sdf_iou=compute_sdf_iou,
+                                          MeshSampledSDFDataset=MeshSampledSDFDataset, OctreeSampledSDFDataset=OctreeSampledSDFDataset))
+    g = torch.Generator().manual_seed(5)
+    batches = []
+    for n in (64, 64, 64, 23):
+        x = torch.rand(n, 3, generator=g) * 1.4 - 0.7
+        batches.append(dict(coords=x, sdf=x.norm(dim=1, keepdim=True) - 0.5))
+    cls = dict(mesh=MeshSampledSDFDataset, octree=OctreeSampledSDFDataset, other=object)[dataset]
+    ds = cls.__new__(cls)
+
+    def trainer():
+        calls = []
+        me = types.SimpleNamespace(train_dataset=ds, train_data_loader=_Loader(batches), device='cpu', epoch=3, max_epochs=10,
+                                   loss_lods=[2] if only_last else [0, 1, 2], pipeline=types.SimpleNamespace(nef=_StubField()),
+                                   cfg=types.SimpleNamespace(only_last=only_last),
+                                   tracker=types.SimpleNamespace(log_metric=lambda *a: calls.append(a)))
+        me._validation_metric_name = types.MethodType(SDFTrainer._validation_metric_name, me)
+        return me, calls
+    a, calls_ref = trainer()
+    b, calls_mine = trainer()
+    if dataset == "other":
+        with pytest.raises(NotImplementedError):
+            ref_validate(a)
+        with pytest.raises(NotImplementedError):
+            SDFTrainer.validate(b)
+        return
+    with caplog.at_level(logging.INFO):
+        caplog.clear()
+        assert ref_validate(a) is None
+        line_ref = [r.getMessage() for r in caplog.records]
+        caplog.clear()
+        out = SDFTrainer.validate(b)
+        line_mine = [r.getMessage() for r in caplog.records]
+    name = "volumetric_iou" if dataset == "mesh" else "narrowband_iou"
+    lods = [2] if only_last else [0, 1, 2]
+    assert calls_mine == calls_ref and len(calls_ref) == len(lods) and calls_ref[0][0] == f"Validation/{name}/{lods[0]}"
+    assert line_mine == line_ref and len(line_ref) == 1 and line_ref[0].startswith(f"EPOCH 3/10 | {name}: ")
+    # the addition: the mean over ALL batches per LOD
+    want = [sum(compute_sdf_iou(_StubField()(coords=bt["coords"], lod_idx=l), bt["sdf"]) for bt in batches) / 4 for l in lods]
+    assert list(out) == [name] and out[name] == pytest.approx(want, rel=1e-12)
+    # ... which is not what the console line shows (scores of the first len(lods) entries over the number of all scores)
+    shown = float(line_ref[0].rsplit(": ", 1)[1])
+    assert abs(shown - sum(c[1] for c in calls_ref) / (4 * len(lods))) < 1e-4
+
+
+def test_render_snapshot_logs_three_cross_sections():
+    from wisp.trainers import SDFTrainer
+    images = []
+    vis = types.SimpleNamespace(sdf_slice=lambda fn, dim=0: np.full((5, 4, 3), 0.1 * dim))
+    nef = types.SimpleNamespace(grid=types.SimpleNamespace(num_lods=3), get_forward_function=lambda name: (lambda x: x))
+    me = types.SimpleNamespace(cfg=types.SimpleNamespace(log_2d=True), epoch=7, device='cpu',
+                               pipeline=types.SimpleNamespace(nef=nef, eval=lambda: None),
+                               tracker=types.SimpleNamespace(visualizer=vis, log_image=lambda *a: images.append(a)))
+    SDFTrainer.render_snapshot(me)
+    assert [i[0] for i in images] == ["Cross-section/X/2", "Cross-section/Y/2", "Cross-section/Z/2"]
+    assert all(i[1].shape == (3, 5, 4) and i[2] == 7 for i in images) and float(images[2][1][0, 0, 0]) == pytest.approx(0.2)
+    me.cfg.log_2d = False
+    SDFTrainer.render_snapshot(me)
+    assert len(images) == 3
+    from wisp.trainers import ConfigSDFTrainer
+    assert ConfigSDFTrainer().valid_every == -1 and ConfigSDFTrainer().log_2d is False
+
+
+def test_render_snapshot_hands_an_offline_renderer_the_field_and_goes_through_sdf_query(monkeypatch):
+    """a foreign visualizer gets the 'sdf' forward function, as in the reference; this package's OfflineRenderer gets the field
+    and evaluates the three slices through wisp.ops.sdf.sdf_query"""
+    import wisp.ops.sdf as S
+    import wisp.trainers.tracker.offline_renderer as mod
+    from wisp.trainers import SDFTrainer
+    from wisp.trainers.tracker import OfflineRenderer
+    fwd = lambda x: x[:, :1]                                                        # noqa: E731
+    nef = types.SimpleNamespace(grid=types.SimpleNamespace(num_lods=2), get_forward_function=lambda name: fwd)
+    seen, images = [], []
+    vis = types.SimpleNamespace(sdf_slice=lambda fn, dim=0: (seen.append(fn), np.zeros((4, 4, 3)))[1])
+    me = types.SimpleNamespace(cfg=types.SimpleNamespace(log_2d=True), epoch=1, device='cpu',
+                               pipeline=types.SimpleNamespace(nef=nef, eval=lambda: None),
+                               tracker=types.SimpleNamespace(visualizer=vis, log_image=lambda *a: images.append(a)))
+    SDFTrainer.render_snapshot(me)
+    assert seen == [fwd, fwd, fwd]
+    queries = []
+
+    def fake_query(field, coords, lod_idx=None, gts=None, counts=None):
+        queries.append((field, tuple(coords.shape), lod_idx))
+        return coords.norm(dim=1, keepdim=True) - 0.5
+    monkeypatch.setattr(S, "sdf_query", fake_query)
+    monkeypatch.setattr(mod, "normalized_slice", lambda w, h, dim=0, depth=0.0, device='cpu': torch.rand(w, h, 3) * 2 - 1)
+    me.tracker = types.SimpleNamespace(visualizer=OfflineRenderer(render_res=(6, 5), device='cpu'), log_image=lambda *a: images.append(a))
+    nef.get_forward_function = lambda name: (_ for _ in ()).throw(AssertionError("the forward function is not what the slices use"))
+    SDFTrainer.render_snapshot(me)
+    assert queries == [(nef, (30, 3), None)] * 3 and len(images) == 6 and images[-1][1].shape == (3, 6, 5)
+    # no visualizer on the tracker: one is made, kept, and handed the field too
+    me.tracker = types.SimpleNamespace(visualizer=None, log_image=lambda *a: images.append(a))
+    monkeypatch.setattr(OfflineRenderer, "sdf_slice", lambda self, fn, dim=0, depth=0: (seen.append(fn), np.zeros((3, 3, 3)))[1])
+    SDFTrainer.render_snapshot(me)
+    assert isinstance(me.tracker.visualizer, OfflineRenderer) and seen[-3:] == [nef, nef, nef]
+
+
+def test_post_epoch_renders_cross_sections_only_when_asked():
+    from wisp.trainers import ConfigSDFTrainer, SDFTrainer
+    from wisp.trainers.base_trainer import _Tracker
+    t = SDFTrainer.__new__(SDFTrainer)
+    t.pipeline = types.SimpleNamespace(eval=lambda: None)
+    t.tracker, t.max_epochs = _Tracker(), 10
+    calls = []
+    t.render_snapshot = lambda: calls.append(t.epoch)
+    for log_2d, every, epoch, want in ((True, 2, 2, True), (True, 2, 3, False), (False, 2, 2, False), (True, -1, 2, False), (True, 1, 5, True)):
+        t.cfg = ConfigSDFTrainer(log_2d=log_2d, render_every=every, resample=False)
+        t.epoch = epoch
+        before = len(calls)
+        t.post_epoch()
+        assert (len(calls) > before) == want, (log_2d, every, epoch)
+    assert calls == [2, 5]
