@@ -38,7 +38,8 @@ const char* wisp_last_error(void);
  * slot scales of the hash-grid backward; 4 = round 4: workspace + row counts of the order-free trilinear / codebook backward.
  * Entry points that are only ADDED - wisp_spc_query_chain, wisp_composite_loss, wisp_codebook_trilinear_multi_bwd,
  * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
- * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient - do not bump it). */
+ * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
+ * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -498,6 +499,51 @@ int wisp_sdf_fd_gradient(const float* coords, int64_t n, const uint8_t* octree, 
                          const int32_t* trinkets, const void* const* feats, int feats_dtype, const int32_t* levels, int num_lods,
                          int channels, int half_round, const float* w1, const float* b1, const float* w2, const float* b2,
                          int hidden, int out_rows, float eps, float* grad, wisp_stream_t stream);
+
+/* The same three evaluations for a NeuralSDF over a HashGrid (nglod_hash.yaml; csrc/hash_sdf_eval.hip): what NeuralSDF.sdf
+ * computes over the grid ops - HashGrid.interpolate (wisp/models/grids/hash_grid.py:205-233: hashgrid_interpolate_cuda.cu:19-339
+ * over all levels, then 'cat' with the columns >= lod_idx * feature_dim zeroed, :226-229, or 'sum' over the levels), then
+ * [position, features] -> Linear -> relu -> Linear (wisp/models/nefs/neural_sdf.py:120-155).  The hash field:
+ *   codebook          MultiTable.feats, [begin_idxes[num_lods], feature_dim] of feats_dtype (f32 / f16 / bf16)
+ *   begin_idxes       HOST int64 [num_lods + 1]: first row of every level and the row count of the whole table
+ *   resolutions       HOST int32 [num_lods]
+ *   feature_dim       2, 4 or 8;  1 <= num_lods <= 16;  coordinates are 3-D
+ *   multiscale        0 = 'cat' (K = num_lods * feature_dim feature columns), 1 = 'sum' (K = feature_dim);  K <= 32
+ *   zero_from_col     level columns l * feature_dim + k at or above it are exactly 0 and not gathered ('cat': lod_idx *
+ *                     feature_dim, 0 is legal - the decoder then sees the position alone; 'sum': num_lods * feature_dim)
+ *   w1 f32 [hidden, 3 + K] in nn.Linear layout, b1 [hidden], w2 [hidden], b2 [1];  1 <= hidden <= 256
+ * Cell, corner indices and blend factors are those of wisp_hashgrid_interpolate_fwd (dense and hashed levels, the clamp of
+ * coordinates outside the cube); there is no occupancy test.  A shape outside these limits returns WISP_ERR_INVALID before any
+ * launch.
+ *
+ * wisp_hash_sdf_query: coords f32 [n,3] -> out f32 [n,1]; gts / counts as for wisp_sdf_query (compute_sdf_iou,
+ * wisp/ops/sdf/metrics.py:12-29, without the read-back per batch of wisp/trainers/sdf_trainer.py:156-190); out may then be
+ * NULL. */
+int wisp_hash_sdf_query(const float* coords, int64_t n, const void* codebook, int feats_dtype, const int64_t* begin_idxes,
+                        const int32_t* resolutions, int num_lods, int feature_dim, int codebook_bitwidth, int multiscale,
+                        int zero_from_col, const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
+                        float* out, const float* gts, int64_t* counts, wisp_stream_t stream);
+
+/* Central-difference gradient of that field in one launch (replaces finitediff_gradient,
+ * wisp/ops/differential/gradients.py:29-45: six field queries): grad[i, a] = (f(x + eps e_a) - f(x - eps e_a)) / (2 eps),
+ * positions and difference in fp32, every value bit for bit what wisp_hash_sdf_query returns at that position.  grad f32 [n,3]. */
+int wisp_hash_sdf_fd_gradient(const float* coords, int64_t n, const void* codebook, int feats_dtype, const int64_t* begin_idxes,
+                              const int32_t* resolutions, int num_lods, int feature_dim, int codebook_bitwidth, int multiscale,
+                              int zero_from_col, const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
+                              float eps, float* grad, wisp_stream_t stream);
+
+/* One marching iteration of PackedSDFTracer.trace (wisp/tracers/packed_sdf_tracer.py:118-146) INCLUDING the field query of
+ * that field: everything wisp_sphere_trace_step does, then dist[p] = (decoder(x[p]) + b2) * scale for the packs still marching,
+ * bit for bit wisp_hash_sdf_query's value at x[p] times scale (first != 0: only the query, for the start positions).  State
+ * arrays and any_active as for wisp_sdf_trace_step_fused. */
+int wisp_hash_sdf_trace_step_fused(int64_t num_packs, int first, const float* nug_o, const float* nug_d, const float* nug_depth,
+                                   const int32_t* nug_pidx, float dist_max, float thr_close, float thr_avg, float* t,
+                                   float* dist, float* dist_prev, uint8_t* mask, uint8_t* hit, const int32_t* curr_in,
+                                   int32_t* curr_out, int64_t* curr_pidx, float* x, const void* codebook, int feats_dtype,
+                                   const int64_t* begin_idxes, const int32_t* resolutions, int num_lods, int feature_dim,
+                                   int codebook_bitwidth, int multiscale, int zero_from_col, const float* w1, const float* b1,
+                                   const float* w2, const float* b2, int hidden, float scale, int32_t* any_active,
+                                   wisp_stream_t stream);
 
 /* Compositing + photometric loss + compositing backward of a TRAINING step in one launch (what
  * wisp/tracers/packed_rf_tracer.py:143-165, wisp/trainers/multiview_trainer.py:140-154 and their autograd backward do in

@@ -1,0 +1,147 @@
+// Field evaluation of the nglod_hash shape as one __device__ function: NeuralSDF over a HashGrid
+// (wisp/models/nefs/neural_sdf.py:120-155 over wisp/models/grids/hash_grid.py:205-233: HashGrid.interpolate 'cat' with the
+// columns from lod_idx * feature_dim on zeroed, or 'sum' over the levels -> [position, features] -> Linear -> relu -> Linear).
+// The hash-grid twin of sdf_eval_point (sdf_eval_dev.h); shared by the three kernels of hash_sdf_eval.hip, so that a value the
+// gradient kernel differences and a distance the marching kernel steps by are bit for bit what the query kernel returns for
+// the same position.
+//
+// 16 lanes own one point.  The level columns l * F + k are handed out in adjacent PAIRS (F is even, so a pair lies in one
+// level and in one table row): lane c blends pairs c, c + 16, ... - one corner_setup (hashgrid_dev.h: the cell, the eight
+// indices and the blend factors are the bits hashgrid_fwd_kernel computes) and eight 8- or 4-byte gathers per pair.  At the
+// nglod_hash shape (4 levels x 8 features) every lane has exactly one pair.  There is no occupancy test: a hash grid answers
+// everywhere, a coordinate outside the cube is clamped by corner_setup.  The blend is the forward kernel's: fp32 fma chain
+// over the corners in corner order, rounded through the table dtype as its store does.  'cat' puts the columns behind the
+// position; 'sum' adds the (rounded) levels in level order in fp32 and rounds through the table dtype once, as
+// Tensor.sum(-2) does on a half tensor.  The decoder is that of sdf_eval_point: hidden layer split over the lanes (weights in
+// LDS), fp32 fma chain in input order, the output dot product reduced with four shuffles of width 16.
+#pragma once
+#include "wisp_common.h"
+#include "hashgrid_dev.h"
+
+#define HSDF_GROUP 16
+#define HSDF_MAX_COLS 32
+#define HSDF_MAX_HIDDEN 256
+#define HSDF_MAX_LODS 16
+
+struct HashSdfField {
+    HashLevels lv;
+    int64_t begin[HSDF_MAX_LODS + 1];         // first table row of every level, and the number of rows of the whole table
+    const void* codebook;                     // MultiTable.feats: [begin[num_lods], feature_dim] of the table dtype
+    uint32_t tsize;                           // 2^codebook_bitwidth
+    int num_lods, feature_dim, sum, zero_from_col, cols, hidden;      // cols = decoder feature columns K
+    const float *w1, *b1, *w2, *b2;           // [hidden, 3 + cols], [hidden], [hidden], [1]
+};
+
+// LDS of a block: W1 [hidden][in_pad], b1 [hidden], w2 [hidden] | per group: the 3 + cols decoder inputs, then ('sum' only) the
+// num_lods * feature_dim level blends
+struct HashSdfLds { float *w1, *b1, *w2, *in; int in_pad, stride; };
+
+static inline int hash_sdf_in_pad(int cols) { return (3 + cols) | 1; }          // odd row stride: the lanes of a group read different rows
+static inline int hash_sdf_group_floats(int cols, int num_lods, int feature_dim, int sum) {
+    return 3 + cols + (sum ? num_lods * feature_dim : 0);
+}
+static inline size_t hash_sdf_lds_bytes(int hidden, int cols, int num_lods, int feature_dim, int sum, int groups) {
+    return ((size_t)hidden * hash_sdf_in_pad(cols) + 2 * (size_t)hidden +
+            (size_t)groups * hash_sdf_group_floats(cols, num_lods, feature_dim, sum)) * sizeof(float);
+}
+
+// every thread of the block; ends with the block barrier
+static __device__ __forceinline__ HashSdfLds hash_sdf_stage(float* base, const HashSdfField& fld) {
+    HashSdfLds s;
+    const int in_dim = 3 + fld.cols;
+    s.in_pad = in_dim | 1;
+    s.stride = in_dim + (fld.sum ? fld.num_lods * fld.feature_dim : 0);
+    s.w1 = base;
+    s.b1 = s.w1 + fld.hidden * s.in_pad;
+    s.w2 = s.b1 + fld.hidden;
+    s.in = s.w2 + fld.hidden;
+    for (int e = threadIdx.x; e < fld.hidden * in_dim; e += blockDim.x) s.w1[(e / in_dim) * s.in_pad + e % in_dim] = fld.w1[e];
+    for (int e = threadIdx.x; e < fld.hidden; e += blockDim.x) { s.b1[e] = fld.b1[e]; s.w2[e] = fld.w2[e]; }
+    __syncthreads();
+    return s;
+}
+
+// two adjacent features of one table row (the pair is 2 * sizeof(T) aligned: even column of a row of an even number of features)
+template <typename T> static __device__ __forceinline__ void hash_sdf_load_pair(const T* p, float& a, float& b);
+template <> __device__ __forceinline__ void hash_sdf_load_pair<float>(const float* p, float& a, float& b) {
+    const float2 v = *reinterpret_cast<const float2*>(p);
+    a = v.x; b = v.y;
+}
+template <> __device__ __forceinline__ void hash_sdf_load_pair<__half>(const __half* p, float& a, float& b) {
+    const __half2 v = *reinterpret_cast<const __half2*>(p);
+    a = __half2float(__low2half(v)); b = __half2float(__high2half(v));
+}
+template <> __device__ __forceinline__ void hash_sdf_load_pair<__hip_bfloat16>(const __hip_bfloat16* p, float& a, float& b) {
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+    a = __uint_as_float(v << 16); b = __uint_as_float(v & 0xffff0000u);
+}
+
+// All 16 lanes of a group call this together, with the same position.  c = lane within the group, gin = the group's floats of
+// LDS.  A group either runs the whole function or none of it (the shuffles stay inside the group).  Returns the raw decoder
+// output with the bias added.  Every rounding is spelled out - explicit fmaf, the compiler's own contraction switched off -
+// for the reason recorded at sdf_eval_coeffs (sdf_eval_dev.h): inlined copies of one function were scheduled differently and
+// returned different bits behind the rounding through a half table dtype.
+template <typename T>
+static __device__ __forceinline__ float hash_sdf_eval_point(const HashSdfField& fld, const HashSdfLds& s, float* gin, int c,
+                                                            float px, float py, float pz) {
+#pragma clang fp contract(off)
+    const float pos[3] = {px, py, pz};
+    const int F = fld.feature_dim;
+    const int level_cols = fld.num_lods * F;
+    float* lev = fld.sum ? gin + 3 + fld.cols : gin + 3;        // 'cat': the level columns ARE the decoder's feature columns
+    const T* __restrict__ table = reinterpret_cast<const T*>(fld.codebook);
+    __builtin_amdgcn_wave_barrier();                           // the previous evaluation's reads of gin are done
+    for (int q = c; 2 * q < level_cols; q += HSDF_GROUP) {
+        const int col = 2 * q;
+        const int l = col / F, k = col - l * F;
+        float a0 = 0.0f, a1 = 0.0f;
+        if (col < fld.zero_from_col) {                         // (a zeroed column is not gathered)
+            CornerSetup<3> cs;
+            const bool dense = fld.lv.dense[l] != 0;
+            corner_setup<3>(pos, fld.lv.res[l], fld.lv.hi[l], fld.lv.hr[l], dense, fld.tsize, true, cs);
+            const int64_t first = fld.begin[l];
+            if (dense) {
+                // hashgrid_fwd_kernel's pin (its comment: at res >= 258 the fp32 clamp bound rounds up and a corner index can
+                // leave the level; below that no index reaches the pin, so it is applied to every dense level here)
+                const int64_t last = fld.begin[fld.num_lods] - 1 - first;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if ((int64_t)(uint32_t)cs.idx[j] > last) cs.idx[j] = (int32_t)last;
+            }
+            float v0[8], v1[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) hash_sdf_load_pair<T>(table + (first + (int64_t)(uint32_t)cs.idx[j]) * F + k, v0[j], v1[j]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                a0 = __builtin_fmaf(v0[j], cs.coef[j], a0);
+                a1 = __builtin_fmaf(v1[j], cs.coef[j], a1);
+            }
+            a0 = Cvt<T>::to_f(Cvt<T>::from_f(a0));
+            a1 = (col + 1 < fld.zero_from_col) ? Cvt<T>::to_f(Cvt<T>::from_f(a1)) : 0.0f;
+        }
+        lev[col] = a0;
+        lev[col + 1] = a1;
+    }
+    if (c < 3) gin[c] = pos[c];
+    __builtin_amdgcn_wave_barrier();                           // the group's lanes are in one wave: LDS order suffices
+    if (fld.sum) {
+        if (c < F) {
+            float acc = 0.0f;
+            for (int l = 0; l < fld.num_lods; ++l) acc += lev[l * F + c];
+            gin[3 + c] = Cvt<T>::to_f(Cvt<T>::from_f(acc));
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    // ---- decoder: in = [position, features]
+    const int in_dim = 3 + fld.cols;
+    float o = 0.0f;
+    for (int hh = c; hh < fld.hidden; hh += HSDF_GROUP) {
+        const float* wr = s.w1 + hh * s.in_pad;
+        float a = s.b1[hh];
+        for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
+        o = __builtin_fmaf(s.w2[hh], fmaxf(a, 0.0f), o);
+    }
+#pragma unroll
+    for (int d = HSDF_GROUP / 2; d >= 1; d >>= 1) o += __shfl_xor(o, d, HSDF_GROUP);
+    return o + fld.b2[0];
+}

@@ -80,6 +80,13 @@ SIGNATURES = {
                        c_vp, c_vp, c_vp, c_vp],
     "wisp_sdf_fd_gradient": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                              c_i32, c_f32, c_vp, c_vp],
+    "wisp_hash_sdf_query": [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                            c_vp, c_vp, c_vp, c_vp],
+    "wisp_hash_sdf_fd_gradient": [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                  c_f32, c_vp, c_vp],
+    "wisp_hash_sdf_trace_step_fused": [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                       c_f32, c_vp, c_vp],
     "wisp_sdf_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32],
     "wisp_sdf_train_step": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
@@ -1333,30 +1340,82 @@ def _sdf_field_args(fld):
             w1.shape[0], rows), (fp, lv)
 
 
+def _hash_sdf_field_args(fld):
+    """the field part of the wisp_hash_sdf_* argument lists from a dict of kind 'hash' (PackedSDFTracer._fused_field)"""
+    cb = fld["codebook"]
+    w1, b1, w2, b2 = fld["w1"], fld["b1"], fld["w2"], fld["b2"]
+    res = [int(r) for r in fld["resolutions"]]
+    begin = [int(b) for b in fld["begin_idxes"]]
+    n, F = len(res), int(fld["feature_dim"])
+    multiscale = {"cat": 0, "sum": 1}[fld["multiscale"]]
+    cols = F if multiscale else n * F
+    assert cb.is_cuda and cb.is_contiguous() and cb.dim() == 2 and cb.shape[1] == F and len(begin) == n + 1 and begin[-1] == cb.shape[0]
+    for a in (w1, b1, w2, b2):
+        assert a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()
+    assert w1.shape[1] == 3 + cols and b1.numel() == w1.shape[0] and w2.numel() == w1.shape[0] and b2.numel() == 1
+    bi = (ctypes.c_int64 * (n + 1))(*begin)
+    rs = (ctypes.c_int32 * n)(*res)
+    return (_p(cb), _DTYPE_CODE[cb.dtype], bi, rs, n, F, int(fld["codebook_bitwidth"]), multiscale, int(fld["zero_from_col"]),
+            _p(w1), _p(b1), _p(w2), _p(b2), w1.shape[0]), (bi, rs)
+
+
+def _is_hash_field(fld):
+    kind = fld.get("kind", "octree")
+    if kind not in ("octree", "hash"):
+        raise ValueError(f"unknown fused SDF field kind {kind!r}")
+    return kind == "hash"
+
+
 def sdf_query(coords, fld, gts=None, counts=None, with_out=True):
     """Field values at coords [n,3] -> f32 [n, rows] (rows = 1, or 4 for a textured field: the decoder's raw outputs), one launch
-    (csrc/sdf_eval.hip).  gts [n] + counts (int64 [2], ADDED to): intersection / union of (pred < 0), (gt < 0) on the distance
-    row; with_out=False returns None and only counts."""
+    (csrc/sdf_eval.hip; a field dict of kind 'hash': csrc/hash_sdf_eval.hip).  gts [n] + counts (int64 [2], ADDED to):
+    intersection / union of (pred < 0), (gt < 0) on the distance row; with_out=False returns None and only counts."""
+    hashed = _is_hash_field(fld)
     coords = _need(coords, torch.float32, "coords")
     n = coords.shape[0]
-    args, keep = _sdf_field_args(fld)
-    out = torch.empty(n, args[-1], dtype=torch.float32, device=coords.device) if with_out else None
+    args, keep = _hash_sdf_field_args(fld) if hashed else _sdf_field_args(fld)
+    out = torch.empty(n, 1 if hashed else args[-1], dtype=torch.float32, device=coords.device) if with_out else None
     if counts is not None:
         gts = _need(gts, torch.float32, "gts").reshape(-1)
         assert gts.shape[0] == n and counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
-    _check(lib.wisp_sdf_query(_p(coords), n, *args, _p(out), _p(gts) if counts is not None else c_vp(0), _p(counts), _stream()),
-           "sdf_query")
+    fn = lib.wisp_hash_sdf_query if hashed else lib.wisp_sdf_query
+    _check(fn(_p(coords), n, *args, _p(out), _p(gts) if counts is not None else c_vp(0), _p(counts), _stream()), "sdf_query")
     return out
 
 
 def sdf_fd_gradient(coords, fld, eps=0.005):
-    """Central-difference gradient [n,3] of the field's distance row at coords [n,3], one launch (csrc/sdf_eval.hip)."""
+    """Central-difference gradient [n,3] of the field's distance row at coords [n,3], one launch (csrc/sdf_eval.hip; kind 'hash':
+    csrc/hash_sdf_eval.hip)."""
     coords = _need(coords, torch.float32, "coords")
     n = coords.shape[0]
-    args, keep = _sdf_field_args(fld)
+    hashed = _is_hash_field(fld)
+    args, keep = _hash_sdf_field_args(fld) if hashed else _sdf_field_args(fld)
     grad = torch.empty(n, 3, dtype=torch.float32, device=coords.device)
-    _check(lib.wisp_sdf_fd_gradient(_p(coords), n, *args, float(np.float32(eps)), _p(grad), _stream()), "sdf_fd_gradient")
+    fn = lib.wisp_hash_sdf_fd_gradient if hashed else lib.wisp_sdf_fd_gradient
+    _check(fn(_p(coords), n, *args, float(np.float32(eps)), _p(grad), _stream()), "sdf_fd_gradient")
     return grad
+
+
+def hash_sdf_trace_step_fused(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit,
+                              curr_in, curr_out, curr_pidx, x, fld, scale, any_active=None):
+    """sphere_trace_step + the NeuralSDF / HashGrid field query at the new positions, one launch (csrc/hash_sdf_eval.hip)."""
+    args, keep = _hash_sdf_field_args(fld)
+    _check(lib.wisp_hash_sdf_trace_step_fused(nug_o.shape[0], int(first), _p(nug_o), _p(nug_d), _p(nug_depth), _p(nug_pidx),
+                                              float(np.float32(dist_max)), float(np.float32(thr_close)), float(np.float32(thr_avg)),
+                                              _p(t), _p(dist), _p(dist_prev), _p(mask), _p(hit), _p(curr_in), _p(curr_out),
+                                              _p(curr_pidx), _p(x), *args, float(np.float32(scale)), _p(any_active), _stream()),
+           "hash_sdf_trace_step_fused")
+
+
+def sdf_trace_step_field(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit,
+                         curr_in, curr_out, curr_pidx, x, fld, scale, any_active=None):
+    """One fused marching iteration on a field dict of PackedSDFTracer._fused_field: the entry point goes by its `kind`."""
+    state = (first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit, curr_in, curr_out,
+             curr_pidx, x)
+    if _is_hash_field(fld):
+        return hash_sdf_trace_step_fused(*state, fld, scale, any_active)
+    return sdf_trace_step_fused(*state, fld["octree"], fld["exsum"], fld["points"], fld["trinkets"], fld["feats"], fld["levels"],
+                                fld["half_round"], fld["w1"], fld["b1"], fld["w2"], fld["b2"], scale, any_active)
 
 
 _sdf_scratch = _Scratch(zeroed=False)      # (SDFTrainStep.capture bakes its address into a HIP graph: _Scratch keeps it alive)

@@ -79,12 +79,18 @@ class PackedSDFTracer(BaseTracer):
         NeuralSDF (nglod_octree.yaml) - OctreeGrid with 16 'sum'-med feature channels, linear interpolation, raw position
         input without embedding, one hidden relu layer with bias.  A NeuralSDFTex of the same shape (four outputs; features
         alone, or the raw position in front of them) marches on its fourth output row.  Anything else marches through
-        `nef(...)` per iteration."""
+        `nef(...)` per iteration.  A plain NeuralSDF over a HashGrid (nglod_hash.yaml) has a branch of its own:
+        _fused_field_hash."""
+        from wisp.models.grids.hash_grid import HashGrid
         from wisp.models.grids.octree_grid import OctreeGrid
         from wisp.models.nefs.neural_sdf import NeuralSDF
         from wisp.models.nefs.neural_sdf_tex import NeuralSDFTex
         import os
-        if os.environ.get("WISP_SDF_FUSED", "1") == "0" or type(nef.grid) is not OctreeGrid:
+        if os.environ.get("WISP_SDF_FUSED", "1") == "0":
+            return None
+        if type(nef.grid) is HashGrid:
+            return PackedSDFTracer._fused_field_hash(nef, lod_idx) if type(nef) is NeuralSDF else None
+        if type(nef.grid) is not OctreeGrid:
             return None
         if type(nef) is NeuralSDFTex:
             return PackedSDFTracer._fused_field_tex(nef, lod_idx)
@@ -138,6 +144,33 @@ class PackedSDFTracer(BaseTracer):
                     w2=dec.lout.weight.detach().float()[3].contiguous(), b2=dec.lout.bias.detach().float()[3:4].contiguous(),
                     octree=g.blas.octree, exsum=g.blas.prefix, points=g.blas.points, trinkets=g.trinkets.int().contiguous())
 
+    @staticmethod
+    def _fused_field_hash(nef, lod_idx):
+        """_fused_field for a plain NeuralSDF over a 3-D HashGrid (csrc/hash_sdf_eval.hip): feature_dim 2, 4 or 8, at most 16
+        levels and 32 feature columns ('cat': num_lods * feature_dim, 'sum': feature_dim), raw position input without embedding,
+        one hidden relu layer of at most 256 units with biases, one output, tables on the GPU.  Any lod_idx the grid accepts:
+        'cat' zeroes the columns from lod_idx * feature_dim on (hash_grid.py:226-229), so at lod_idx 0 the decoder sees the
+        position alone.  The dict carries kind='hash'; wisp._C dispatches on it."""
+        g, dec = nef.grid, nef.decoder
+        tables = g.codebook.feats
+        if (g.coord_dim != 3 or g.multiscale_type not in ('cat', 'sum') or g.feature_dim not in (2, 4, 8)
+                or not 1 <= g.num_lods <= 16 or not 0 <= lod_idx < g.num_lods
+                or (g.num_lods * g.feature_dim if g.multiscale_type == 'cat' else g.feature_dim) > 32
+                or not nef.position_input or not isinstance(nef.pos_embedder, torch.nn.Identity)
+                or nef.activation_type != 'relu' or nef.num_layers != 1 or len(dec.layers) != 1 or dec.skip
+                or type(dec.layers[0]) is not torch.nn.Linear or type(dec.lout) is not torch.nn.Linear
+                or dec.layers[0].bias is None or dec.lout.bias is None or dec.lout.out_features != 1
+                or dec.layers[0].out_features > 256 or not tables.is_cuda
+                or tables.dtype not in (torch.float32, torch.float16, torch.bfloat16)):
+            return None
+        cat = g.multiscale_type == 'cat'
+        return dict(kind='hash', codebook=tables.detach().contiguous(), begin_idxes=[int(b) for b in g.codebook.begin_idxes.tolist()],
+                    resolutions=[int(r) for r in g.resolutions], feature_dim=int(g.feature_dim),
+                    codebook_bitwidth=int(g.codebook_bitwidth), multiscale=g.multiscale_type,
+                    zero_from_col=(lod_idx if cat else g.num_lods) * g.feature_dim,
+                    w1=dec.layers[0].weight.detach().float().contiguous(), b1=dec.layers[0].bias.detach().float().contiguous(),
+                    w2=dec.lout.weight.detach().float().reshape(-1).contiguous(), b2=dec.lout.bias.detach().float().contiguous())
+
     def _march_fused(self, fld, rays, rt_pidx, depth, st, num_steps, step_size, min_dis):
         """All marching iterations as one launch each, no host decision per iteration: the loop only peeks at a device
         counter of still-marching packs every 8 iterations (the reference reads `mask.any()` twice per iteration)."""
@@ -145,10 +178,8 @@ class PackedSDFTracer(BaseTracer):
         counter = torch.zeros(1, dtype=torch.int32, device=st.t.device)
 
         def launch(first, cnt):
-            _C.sdf_trace_step_fused(first, st.o, st.d, depth, rt_pidx, rays.dist_max, min_dis, min_dis * 5, st.t, st.dist,
-                                    st.dist_prev, st.active, st.hit, st.nug, st.nug_next, st.cell, st.x, fld["octree"],
-                                    fld["exsum"], fld["points"], fld["trinkets"], fld["feats"], fld["levels"], fld["half_round"],
-                                    fld["w1"], fld["b1"], fld["w2"], fld["b2"], step_size, cnt)
+            _C.sdf_trace_step_field(first, st.o, st.d, depth, rt_pidx, rays.dist_max, min_dis, min_dis * 5, st.t, st.dist,
+                                    st.dist_prev, st.active, st.hit, st.nug, st.nug_next, st.cell, st.x, fld, step_size, cnt)
         launch(True, None)
         st.dist_prev.copy_(st.dist)
         for it in range(num_steps):

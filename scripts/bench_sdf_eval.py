@@ -8,6 +8,9 @@ synchronisation (the host work between launches is part of what is compared):
   normals   central-difference normals at 2^16 points near the surface
   render    OfflineRenderer.render_lookat at 512 x 512 (WISP_SDF_FUSED=0 takes the MARCH through the modular loop as well: this row is
             march + normals, not the normals kernel alone)
+
+--grid hash measures the same three on the field of nglod_hash.yaml (HashGrid.from_geometric, 'cat', 4 levels x 8 features, 16 ..
+2048, tables of 2^--codebook-bitwidth rows; csrc/hash_sdf_eval.hip) and writes profiles/bench_hash_sdf_eval.json.
 """
 import argparse
 import json
@@ -55,8 +58,12 @@ def main(argv=None):
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--epochs", type=int, default=2, help="epochs of fitting before measuring (the render needs a surface)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_sdf_eval.json"))
+    ap.add_argument("--grid", choices=("octree", "hash"), default="octree")
+    ap.add_argument("--codebook-bitwidth", type=int, default=19, help="--grid hash: the hashed levels have 2^N rows")
+    ap.add_argument("--out", default=None, help="default: profiles/bench_sdf_eval.json, bench_hash_sdf_eval.json with --grid hash")
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "bench_hash_sdf_eval.json" if args.grid == "hash" else "bench_sdf_eval.json")
     logging.basicConfig(level=logging.WARNING)
     import train_nglod
     from train_sdf_tex import write_test_mesh
@@ -68,14 +75,16 @@ def main(argv=None):
     torch.manual_seed(0)
     with tempfile.TemporaryDirectory() as tmp:
         obj = write_test_mesh(tmp)
-        ds, pipeline = train_nglod.build(obj, dev, level=args.level, num_samples=args.num_samples)
+        ds, pipeline = train_nglod.build(obj, dev, level=args.level, num_samples=args.num_samples, grid_type=args.grid,
+                                         codebook_bitwidth=args.codebook_bitwidth)
     cfg = ConfigSDFTrainer(optimizer=ConfigAdam(lr=1e-3, eps=1e-15), dataloader=ConfigDataloader(batch_size=512),
                            max_epochs=args.epochs, resample=False, only_last=True, profile_nvtx=False)
     trainer = SDFTrainer(cfg, pipeline, ds, device=dev)
     train_nglod.fit_fused(trainer, ds, cfg, dev)
     nef = pipeline.nef
     assert fused_sdf_field(nef, None) is not None
-    rec = dict(bench="sdf_eval", device=torch.cuda.get_device_name(0), level=args.level, lods=nef.grid.num_lods, hidden=128,
+    rec = dict(bench="hash_sdf_eval" if args.grid == "hash" else "sdf_eval", device=torch.cuda.get_device_name(0), level=args.level,
+               lods=nef.grid.num_lods, hidden=128, **(dict(codebook_bitwidth=args.codebook_bitwidth) if args.grid == "hash" else {}),
                dataset_points=len(ds), batches=len(trainer.train_data_loader), reps=args.reps)
     iou = {}
 

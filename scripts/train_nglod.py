@@ -2,12 +2,16 @@
 OctreeAS.from_mesh, OctreeGrid, NeuralSDF, a mesh SDF dataset, SDFTrainer with its IoU validation - then an OfflineRenderer
 snapshot (render.png) and the three axis-aligned distance cross-sections (slice_x.png, slice_y.png, slice_z.png).
 
-    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--fused-step] [--out-dir DIR]
+    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--grid octree|hash] [--fused-step] [--out-dir DIR]
     python scripts/train_nglod.py --write-test-mesh DIR ...
 
 --write-test-mesh DIR first writes the procedural torus of scripts/train_sdf_tex.py into DIR and fits that.
 --fused-step trains with SDFTrainStep (flat parameter buffer, single-launch optimizer, fused forward + loss + backward, replayed
 as a HIP graph for whole batches) instead of SDFTrainer's torch.optim loop; validation is SDFTrainer.validate either way.
+--grid hash fits the field of nglod_hash.yaml instead: HashGrid.from_geometric, 'cat', 4 levels x 8 features between resolutions
+16 and 2048, tables of 2^19 rows (--codebook-bitwidth for smaller ones).  Validation, the snapshot and the slices then run through
+the kernels of csrc/hash_sdf_eval.hip; SDFTrainStep has no fused step for a hash grid, so --fused-step trains through its modular
+launches there (and without the graph).
 The last line printed is one JSON record with the IoU before and after training."""
 import argparse
 import json
@@ -24,12 +28,12 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd"), os.path.join(ROOT, 
 
 
 def build(obj, device, level=6, dataset="octree", num_samples=100000, samples_per_voxel=16, num_lods=4, hidden_dim=128,
-          num_samples_on_mesh=2_000_000):
-    """(dataset, pipeline) as main_nglod.py builds them from nglod_octree.yaml."""
+          num_samples_on_mesh=2_000_000, grid_type="octree", codebook_bitwidth=19):
+    """(dataset, pipeline) as main_nglod.py builds them from nglod_octree.yaml (grid_type 'octree') or nglod_hash.yaml ('hash')."""
     from wisp.accelstructs import OctreeAS
     from wisp.datasets import MeshSampledSDFDataset, OctreeSampledSDFDataset
     from wisp.models import Pipeline
-    from wisp.models.grids import OctreeGrid
+    from wisp.models.grids import HashGrid, OctreeGrid
     from wisp.models.nefs import NeuralSDF
     from wisp.tracers import PackedSDFTracer
     blas = OctreeAS.from_mesh(obj, level=level, num_samples_on_mesh=num_samples_on_mesh)
@@ -37,7 +41,11 @@ def build(obj, device, level=6, dataset="octree", num_samples=100000, samples_pe
         ds = OctreeSampledSDFDataset(blas, split='train', num_samples=num_samples, samples_per_voxel=samples_per_voxel)
     else:
         ds = MeshSampledSDFDataset(obj, split='train', num_samples=max(num_samples // 5, 1))
-    grid = OctreeGrid(blas, feature_dim=16, num_lods=num_lods, multiscale_type='sum', feature_std=0.01)
+    if grid_type == "hash":
+        grid = HashGrid.from_geometric(blas, feature_dim=8, num_lods=num_lods, multiscale_type='cat', feature_std=0.01,
+                                       codebook_bitwidth=codebook_bitwidth, min_grid_res=16, max_grid_res=2048)
+    else:
+        grid = OctreeGrid(blas, feature_dim=16, num_lods=num_lods, multiscale_type='sum', feature_std=0.01)
     nef = NeuralSDF(grid, pos_embedder='none', position_input=True, hidden_dim=hidden_dim, num_layers=1).to(device)
     return ds, Pipeline(nef, PackedSDFTracer(num_steps=128, step_size=0.8, min_dis=0.0003))
 
@@ -49,7 +57,8 @@ def fit_fused(trainer, ds, cfg, device):
     nef = trainer.pipeline.nef
     step = SDFTrainStep(nef, lr=oc.lr, eps=oc.eps, grid_lr_weight=cfg.grid_lr_weight, betas=oc.betas, optimizer='adam',
                         only_last=cfg.only_last)
-    if torch.device(device).type == 'cuda' and len(ds) >= bs:
+    from wisp.models.grids import OctreeGrid
+    if torch.device(device).type == 'cuda' and len(ds) >= bs and type(nef.grid) is OctreeGrid:
         step.capture(bs)
     nef.train()
     for epoch in range(cfg.max_epochs):
@@ -72,6 +81,8 @@ def main(argv=None):
     ap.add_argument("--write-test-mesh", metavar="DIR")
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--dataset", choices=("octree", "mesh"), default="octree")
+    ap.add_argument("--grid", choices=("octree", "hash"), default="octree", help="feature grid: nglod_octree.yaml or nglod_hash.yaml")
+    ap.add_argument("--codebook-bitwidth", type=int, default=19, help="--grid hash: the hashed levels have 2^N rows")
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--num-lods", type=int, default=4)
     ap.add_argument("--num-samples", type=int, default=100000)
@@ -98,7 +109,8 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     ds, pipeline = build(obj, args.device, level=args.level, dataset=args.dataset, num_samples=args.num_samples,
-                         num_lods=args.num_lods, num_samples_on_mesh=args.mesh_samples)
+                         num_lods=args.num_lods, num_samples_on_mesh=args.mesh_samples, grid_type=args.grid,
+                         codebook_bitwidth=args.codebook_bitwidth)
     cfg = ConfigSDFTrainer(optimizer=ConfigAdam(lr=1e-3, eps=1e-15), dataloader=ConfigDataloader(batch_size=args.batch_size),
                            max_epochs=args.epochs, resample=True, only_last=True, exp_name='nglod', profile_nvtx=False,
                            valid_every=-1)
@@ -127,7 +139,7 @@ def main(argv=None):
         files[f"slice_{name}"] = os.path.join(args.out_dir, f"slice_{name}.png")
         vis = renderer.sdf_slice(pipeline.nef, dim=axis)
         save_u8(files[f"slice_{name}"], (np.clip(vis, 0, 1) * 255).round().astype(np.uint8).transpose(1, 0, 2))
-    rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
+    rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, grid=args.grid, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
                metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
                seconds=round(seconds, 3), **{k: os.path.abspath(v) for k, v in files.items()})
     print(json.dumps(rec))
