@@ -39,7 +39,8 @@ const char* wisp_last_error(void);
  * Entry points that are only ADDED - wisp_spc_query_chain, wisp_composite_loss, wisp_codebook_trilinear_multi_bwd,
  * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
  * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
- * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused - do not bump it). */
+ * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused, wisp_raymarch_ray_emit_coded, wisp_nerf_mlp_operand_image_bytes,
+ * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -387,6 +388,22 @@ int wisp_raymarch_ray_emit(const float* origins, const float* dirs, int64_t num_
                            float* sample_dirs /* f32 [S,3] = dirs[ridx] (rays.dirs.index_select(0, ridx),
                                                  packed_rf_tracer.py:120), or NULL */,
                            wisp_stream_t stream);
+/* wisp_raymarch_ray_emit that also writes the decoder's per-ray view code: dir_code = bf16 [num_rays][32], the buffer
+ * wisp_nerf_mlp_dir_code fills from the same `dirs`, bit for bit, for EVERY ray (rays without samples included).  Replaces the
+ * pair wisp_raymarch_ray_emit + wisp_nerf_mlp_dir_code of a training step (one launch less); all other outputs are
+ * wisp_raymarch_ray_emit's.  view_freqs must be 4.
+ * operand_image (optional, else NULL): wisp_nerf_mlp_operand_image_bytes(hidden) bytes that workgroups behind the rays' fill with
+ * the decoder's operand image of dec_params / in_dim / hidden, byte for byte what wisp_nerf_mlp_build_operand_image writes
+ * (replaces a launch of that entry point).  With NULL nothing but the emit outputs and dir_code is written and dec_params, in_dim
+ * and hidden are not looked at. */
+int wisp_raymarch_ray_emit_coded(const float* origins, const float* dirs, int64_t num_rays,
+                                 float near, float range, int num_samples,
+                                 const float* jitter, uint64_t seed,
+                                 const uint32_t* hitmask, const int64_t* offsets,
+                                 int64_t* ridx, float* samples, float* depth_samples, float* deltas,
+                                 uint8_t* boundary, float* sample_dirs, int view_freqs, void* dir_code,
+                                 const float* dec_params, int in_dim, int hidden, void* operand_image,
+                                 wisp_stream_t stream);
 
 /* 'voxel' mode: num_samples jittered samples inside every nugget; S = M*num_samples.
  * nug_ridx i32 [M], nug_depth f32 [M,2]; jitter f32 [M,N] or NULL (+seed). */
@@ -625,6 +642,24 @@ int wisp_nerf_mlp_bwd_rays(const void* feats, int dtype_io, const void* dir_code
                            int in_dim, int hidden, int view_freqs, const float* params, const float* grad_rgb,
                            const float* grad_density, void* grad_feats, float* grad_params, float* workspace,
                            int64_t workspace_bytes, wisp_stream_t stream);
+/* The two entry points above with the decoder's operands prebuilt.  Every workgroup of wisp_nerf_mlp_fwd_rays / _bwd_rays (~770 per
+ * step) fetches the same fp32 parameters and converts them into the same permuted bf16 operand images in LDS; here that is done
+ * ONCE per change of the parameters and the kernels copy the result:
+ *   wisp_nerf_mlp_operand_image_bytes(hidden)  size of the image (hidden 64; a negative error code otherwise)
+ *   wisp_nerf_mlp_build_operand_image          params (packed as for the entry points above, W1 in_dim wide) -> image
+ *   wisp_nerf_mlp_fwd_rays_img / _bwd_rays_img replace wisp_nerf_mlp_fwd_rays / _bwd_rays: same arguments plus `image`, same results
+ *                                              bit for bit.  `image` must have been built from `params` and `in_dim` as they are
+ *                                              now (the kernels read the image only; rebuild it after an optimizer step).
+ * Hidden 64 and bf16 compute only: any other shape returns the error the _rays entry points return for an unsupported shape. */
+int64_t wisp_nerf_mlp_operand_image_bytes(int hidden);
+int wisp_nerf_mlp_build_operand_image(const float* params, int in_dim, int hidden, void* image, wisp_stream_t stream);
+int wisp_nerf_mlp_fwd_rays_img(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx, int64_t num_samples,
+                               int in_dim, int hidden, int view_freqs, const float* params, const void* image, float* rgb,
+                               float* density, wisp_stream_t stream);
+int wisp_nerf_mlp_bwd_rays_img(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx, int64_t num_samples,
+                               int in_dim, int hidden, int view_freqs, const float* params, const void* image,
+                               const float* grad_rgb, const float* grad_density, void* grad_feats, float* grad_params,
+                               float* workspace, int64_t workspace_bytes, wisp_stream_t stream);
 
 /* One-hidden-layer relu decoder with a single output, out = W2 relu(W1 x + b1) + b2 - the NeuralSDF decoder
  * (wisp/models/nefs/neural_sdf.py:102-118; nglod_octree.yaml: 19 -> 128 -> 1; BasicDecoder.forward,

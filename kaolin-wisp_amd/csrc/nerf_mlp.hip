@@ -587,3 +587,52 @@ extern "C" int wisp_nerf_mlp_bwd_rays(const void* feats, int dtype_io, const voi
     WISP_CHECK_LAUNCH();
     return WISP_OK;
 }
+
+// ---- the per-ray kernels with prebuilt operand images (hidden 64, bf16 compute) -----------------------------------------------
+// Every workgroup of the two decoder launches used to fetch the same fp32 parameters and convert them into the same permuted bf16
+// operand images; here that is done once (wisp_nerf_mlp_build_operand_image, or the tail of wisp_raymarch_ray_emit_coded) and the
+// kernels copy the image.  The image stands for the parameters it was built from: rebuild it after every change of them.
+extern "C" int64_t wisp_nerf_mlp_operand_image_bytes(int hidden) {
+    if (hidden != H) return wisp_fail(WISP_ERR_UNSUPPORTED, "nerf_mlp_rays", "operand images: hidden 64");
+    return wisp_mlp::bf16_operand_image_bytes();
+}
+
+extern "C" int wisp_nerf_mlp_build_operand_image(const float* params, int in_dim, int hidden, void* image, wisp_stream_t stream) {
+    if (hidden != H || in_dim < 1 || in_dim > IN)
+        return wisp_fail(WISP_ERR_UNSUPPORTED, "nerf_mlp_rays", "operand images: 1 <= in_dim <= 32, hidden 64");
+    WISP_REQUIRE(params && image, "null pointer");
+    wisp_mlp::bf16_build_operand_image(params, in_dim, image, (hipStream_t)stream);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
+extern "C" int wisp_nerf_mlp_fwd_rays_img(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx,
+                                          int64_t num_samples, int in_dim, int hidden, int view_freqs, const float* params,
+                                          const void* image, float* rgb, float* density, wisp_stream_t stream) {
+    WISP_REQUIRE(num_samples >= 0, "negative count");
+    if (int rc = check_rays_shape(in_dim, hidden, view_freqs, dtype_io)) return rc;
+    if (num_samples == 0) return WISP_OK;
+    WISP_REQUIRE(feats && dir_code && ridx && params && image && rgb && density, "null pointer");
+    if (int rc = wisp_mlp::bf16_forward_rays_img(feats, dtype_io, dir_code, ridx, num_samples, in_dim, image, rgb, density, (hipStream_t)stream))
+        return rc;
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
+extern "C" int wisp_nerf_mlp_bwd_rays_img(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx,
+                                          int64_t num_samples, int in_dim, int hidden, int view_freqs, const float* params,
+                                          const void* image, const float* grad_rgb, const float* grad_density, void* grad_feats,
+                                          float* grad_params, float* workspace, int64_t workspace_bytes, wisp_stream_t stream) {
+    WISP_REQUIRE(num_samples >= 0, "negative count");
+    if (int rc = check_rays_shape(in_dim, hidden, view_freqs, dtype_io)) return rc;
+    if (num_samples == 0) return WISP_OK;
+    WISP_REQUIRE(feats && dir_code && ridx && params && image && grad_rgb && grad_density && grad_feats && grad_params && workspace, "null pointer");
+    WISP_REQUIRE(workspace_bytes >= wisp_nerf_mlp_bwd_workspace_bytes(num_samples, hidden), "workspace too small (wisp_nerf_mlp_bwd_workspace_bytes)");
+    int rows = 0;
+    if (int rc = wisp_mlp::bf16_backward_rays_img(feats, dtype_io, dir_code, ridx, num_samples, in_dim, image, grad_rgb, grad_density,
+                                                  grad_feats, workspace, &rows, (hipStream_t)stream))
+        return rc;
+    hipLaunchKernelGGL(nerf_mlp_reduce_kernel, dim3((NPARAM + 63) / 64), dim3(1024), 0, (hipStream_t)stream, workspace, rows, in_dim, grad_params);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}

@@ -26,29 +26,14 @@
 #include <cstdlib>
 
 #include "nerf_mlp_bf16_dev.h"
+#include "nerf_mlp_image_dev.h"
 
 namespace {
 using namespace wisp_mlp;
 using namespace wisp_mlp_dev;
 
 
-// forward operands  [out row][K slots], row stride = K + 8 elements
-constexpr int LD1 = 40, LD2 = 72, LD3 = 56, LD4 = 72, LD5 = 72;
-constexpr int L_W1 = 0;                     // [64][32]  natural K (the grid features come straight from HBM)
-constexpr int L_W2 = L_W1 + 64 * LD1;       // [16][64]  chained K
-constexpr int L_W3 = L_W2 + 16 * LD2;       // [64][48]  block 0 chained (density-MLP outputs), blocks 1-2 view encoding
-constexpr int L_W4 = L_W3 + 64 * LD3;       // [64][64]  chained
-constexpr int L_W5 = L_W4 + 64 * LD4;       // [ 4][64]  chained (3 real rows)
-constexpr int L_FWD_END = L_W5 + 4 * LD5;
-// backward operands [in row][out-neuron slots]
-constexpr int LT5 = 24, LT4 = 72, LT3 = 72, LT2 = 24, LT1 = 72;
-constexpr int L_W5T = L_FWD_END;            // [64][16]  slot p < 3 <-> colour channel p
-constexpr int L_W4T = L_W5T + 64 * LT5;     // [64][64]
-constexpr int L_W3T = L_W4T + 64 * LT4;     // [16][64]  row m <-> density-MLP output m (row 0 unused)
-constexpr int L_W2T = L_W3T + 16 * LT3;     // [64][16]
-constexpr int L_W1T = L_W2T + 64 * LT2;     // [32][64]
-constexpr int L_BWD_END = L_W1T + 32 * LT1;
-
+// (the operand layout L_W1 .. L_BWD_END and the global-memory image of it: nerf_mlp_image_dev.h)
 constexpr int TILE_BYTES = 8 * TILE_REGION; // 64 features x 32 samples
 
 // Prologue: the packed fp32 parameters are first copied to an LDS staging area with coalesced loads (one global
@@ -100,7 +85,6 @@ struct LaneConst {
     float b2[8], b5[3];
 };
 
-constexpr int BIASV_FLOATS = 2 * 2 * 2 * 16;
 DEV void stage_bias_vectors(float* biasv, const float* P, int tid, int nthreads) {
     for (int e = tid; e < BIASV_FLOATS; e += nthreads) {
         const int r = e & 15, g = (e >> 4) & 1, t = (e >> 5) & 1, layer = e >> 6;
@@ -130,6 +114,23 @@ DEV void lane_const(LaneConst& L, const __bf16* sw, const float* P, int lane, co
     for (int r = 0; r < 8; ++r) L.b2[r] = P[OB2 + acc_row(r, L.g)];
 #pragma unroll
     for (int c = 0; c < 3; ++c) L.b5[c] = P[OB5 + c];
+}
+
+// the image kernels' lane constants: operand rows and bias vectors in the LDS copy of the image, b2 / b5 from its fp32 tail
+DEV void lane_const_img(LaneConst& L, const unsigned char* img, int lane) {
+    const __bf16* sw = reinterpret_cast<const __bf16*>(img);
+    const float* small = reinterpret_cast<const float*>(img + IMG_OFF_SMALL);
+    L.n = lane & 31; L.g = lane >> 5;
+    L.w1 = sw + L_W1 + L.n * LD1 + 8 * L.g;
+    L.w2 = sw + L_W2 + (L.n & 15) * LD2 + 8 * L.g;
+    L.w3 = sw + L_W3 + L.n * LD3 + 8 * L.g;
+    L.w4 = sw + L_W4 + L.n * LD4 + 8 * L.g;
+    L.w5 = sw + L_W5 + (L.n < 3 ? L.n : 3) * LD5 + 8 * L.g;
+    L.bias_lds = reinterpret_cast<const float*>(img + IMG_OFF_BIASV) + 16 * L.g;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) L.b2[r] = small[acc_row(r, L.g)];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) L.b5[c] = small[16 + c];
 }
 
 // forward of one tile; x0 and the view direction are already in registers
@@ -244,25 +245,11 @@ constexpr int FWD_WAVES = 8;
 constexpr int FWD_OFF_BIASV = L_FWD_END * 2;
 constexpr int FWD_OFF_STG = FWD_OFF_BIASV + BIASV_FLOATS * 4;
 constexpr int FWD_LDS = FWD_OFF_STG + NPARAM_PAD * 4;
-template <typename TIO, bool NARROW, bool PIN, bool CODED = false>
-__global__ void __launch_bounds__(FWD_WAVES * 64)
-mlp_fwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, const int64_t* __restrict__ ridx,
-               int64_t num_samples, int in_dim,
-               const float* __restrict__ params, float* __restrict__ out_rgb, float* __restrict__ out_density) {
-    const bf16x8* code = reinterpret_cast<const bf16x8*>(dirs);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __bf16* sw = reinterpret_cast<__bf16*>(smem);
-    float* biasv = reinterpret_cast<float*>(smem + FWD_OFF_BIASV);
-    float* stg = reinterpret_cast<float*>(smem + FWD_OFF_STG);
-    stage_params<FWD_WAVES * 64>(stg, params, threadIdx.x, NARROW ? in_dim : IN);
-    __syncthreads();
-    stage_weights<false>(sw, stg, threadIdx.x, FWD_WAVES * 64);
-    if (PIN) stage_bias_vectors(biasv, stg, threadIdx.x, FWD_WAVES * 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    LaneConst L;
-    lane_const<PIN>(L, sw, stg, lane, biasv);
-    __syncthreads();
-
+// the tile loop of a forward workgroup (the staged operands are in LDS, L points into them)
+template <typename TIO, bool NARROW, bool PIN, bool CODED>
+DEV void fwd_tiles(const LaneConst& L, int wave, const TIO* __restrict__ feats, const float* __restrict__ dirs, const bf16x8* __restrict__ code,
+                   const int64_t* __restrict__ ridx, int64_t num_samples, int in_dim, float* __restrict__ out_rgb,
+                   float* __restrict__ out_density) {
     const int64_t ntiles = (num_samples + TS - 1) / TS;
     const int64_t stride = (int64_t)gridDim.x * FWD_WAVES;
     int64_t tile = (int64_t)blockIdx.x * FWD_WAVES + wave;
@@ -295,6 +282,51 @@ mlp_fwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, co
             else { d[0] = nd[0]; d[1] = nd[1]; d[2] = nd[2]; }
         }
     }
+}
+
+template <typename TIO, bool NARROW, bool PIN, bool CODED = false>
+__global__ void __launch_bounds__(FWD_WAVES * 64)
+mlp_fwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, const int64_t* __restrict__ ridx,
+               int64_t num_samples, int in_dim,
+               const float* __restrict__ params, float* __restrict__ out_rgb, float* __restrict__ out_density) {
+    const bf16x8* code = reinterpret_cast<const bf16x8*>(dirs);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __bf16* sw = reinterpret_cast<__bf16*>(smem);
+    float* biasv = reinterpret_cast<float*>(smem + FWD_OFF_BIASV);
+    float* stg = reinterpret_cast<float*>(smem + FWD_OFF_STG);
+    stage_params<FWD_WAVES * 64>(stg, params, threadIdx.x, NARROW ? in_dim : IN);
+    __syncthreads();
+    stage_weights<false>(sw, stg, threadIdx.x, FWD_WAVES * 64);
+    if (PIN) stage_bias_vectors(biasv, stg, threadIdx.x, FWD_WAVES * 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    LaneConst L;
+    lane_const<PIN>(L, sw, stg, lane, biasv);
+    __syncthreads();
+
+    fwd_tiles<TIO, NARROW, PIN, CODED>(L, wave, feats, dirs, code, ridx, num_samples, in_dim, out_rgb, out_density);
+}
+
+// mlp_fwd_kernel<TIO, NARROW, PIN = true, CODED = true> with its operands copied from the prebuilt image (nerf_mlp_image_dev.h):
+// 25 KB of LDS instead of 66, one barrier, no conversion.  Same forward_tile, same values.
+template <typename TIO, bool NARROW>
+__global__ void __launch_bounds__(FWD_WAVES * 64)
+mlp_fwd_img_kernel(const TIO* __restrict__ feats, const bf16x8* __restrict__ code, const int64_t* __restrict__ ridx,
+                   int64_t num_samples, int in_dim, const unsigned char* __restrict__ image, float* __restrict__ out_rgb,
+                   float* __restrict__ out_density) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    copy_image<FWD_WAVES * 64, IMG_FWD_BYTES>(smem, image, threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    LaneConst L;
+    lane_const_img(L, smem, lane);
+    fwd_tiles<TIO, NARROW, true, true>(L, wave, feats, nullptr, code, ridx, num_samples, in_dim, out_rgb, out_density);
+}
+
+// stand-alone builder of the image (a training step builds it in the tail of its emit launch: raymarch.hip)
+__global__ void __launch_bounds__(256)
+mlp_operand_image_kernel(const float* __restrict__ params, int in_dim, unsigned char* __restrict__ image) {
+    const int u = blockIdx.x * 256 + threadIdx.x;
+    if (u < IMG_UNITS) build_image_unit(params, in_dim, image, u);
 }
 
 // ---------------------------------------------------------------------------------------------- backward kernel
@@ -410,30 +442,17 @@ DEV void accumulate_stage(const unsigned char* imgY, const unsigned char* imgX, 
     }
 }
 
-template <typename TIO, bool NARROW, bool CODED = false>
-__global__ void __launch_bounds__(BWD_THREADS)
-mlp_bwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, const int64_t* __restrict__ ridx,
-               int64_t num_samples, int in_dim,
-               const float* __restrict__ params, const float* __restrict__ grad_rgb, const float* __restrict__ grad_density,
-               TIO* __restrict__ grad_feats, float* __restrict__ partials) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __bf16* sw = reinterpret_cast<__bf16*>(smem);
-    float* biasv = reinterpret_cast<float*>(smem + BWD_OFF_BIASV);
-    int* flags = reinterpret_cast<int*>(smem + BWD_OFF_FLAGS);              // ready[4], done[4]
-    float* stg = reinterpret_cast<float*>(smem + BWD_OFF_IMG);              // aliases the images
-    stage_params<BWD_THREADS>(stg, params, threadIdx.x, NARROW ? in_dim : IN);
-    if (threadIdx.x < 16) flags[threadIdx.x] = 0;
-    __syncthreads();
-    stage_weights<true>(sw, stg, threadIdx.x, BWD_THREADS);
-    stage_bias_vectors(biasv, stg, threadIdx.x, BWD_THREADS);
+// The main loop and the epilogue of a backward workgroup.  The staged operands are in LDS (L points into the forward ones, `swt` +
+// L_W5T .. are the transposed ones), `flags` are zero, `work` is the region of the pairs' rings (the epilogue's scratch aliases it).
+template <typename TIO, bool NARROW, bool CODED>
+DEV void bwd_tiles(const LaneConst& L, const __bf16* swt, int* flags, unsigned char* work, const TIO* __restrict__ feats,
+                   const float* __restrict__ dirs, const int64_t* __restrict__ ridx, int64_t num_samples, int in_dim,
+                   const float* __restrict__ grad_rgb, const float* __restrict__ grad_density, TIO* __restrict__ grad_feats,
+                   float* __restrict__ partials) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pair = wave & (BWD_PAIRS - 1);
     const bool chain_role = wave < BWD_PAIRS;
-    LaneConst L;
-    lane_const<true>(L, sw, stg, lane, biasv);
-    __syncthreads();
-
-    unsigned char* ring = smem + BWD_OFF_IMG + (size_t)pair * BWD_PAIR_LDS;
+    unsigned char* ring = work + (size_t)pair * BWD_PAIR_LDS;
     int* ready = flags + pair;
     int* done = flags + BWD_PAIRS + pair;
     const int64_t ntiles = (num_samples + TS - 1) / TS;
@@ -444,11 +463,11 @@ mlp_bwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, co
 
     if (chain_role) {
         const int n = L.n, g = L.g;
-        const __bf16* w5t = sw + L_W5T + n * LT5 + 8 * g;                   // this lane's rows of the transposed operands
-        const __bf16* w4t = sw + L_W4T + n * LT4 + 8 * g;
-        const __bf16* w3t = sw + L_W3T + (n & 15) * LT3 + 8 * g;
-        const __bf16* w2t = sw + L_W2T + n * LT2 + 8 * g;
-        const __bf16* w1t = sw + L_W1T + n * LT1 + 8 * g;
+        const __bf16* w5t = swt + L_W5T + n * LT5 + 8 * g;                  // this lane's rows of the transposed operands
+        const __bf16* w4t = swt + L_W4T + n * LT4 + 8 * g;
+        const __bf16* w3t = swt + L_W3T + (n & 15) * LT3 + 8 * g;
+        const __bf16* w2t = swt + L_W2T + n * LT2 + 8 * g;
+        const __bf16* w1t = swt + L_W1T + n * LT1 + 8 * g;
         const int wc_off = (2 * n + g) * 8, wn_off = g * TILE_REGION + n * 16;
         Acts A;
         float d[3] = {0.f, 0.f, 0.f};
@@ -588,7 +607,7 @@ mlp_bwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, co
     // LDS next to the weights) the accumulator waves park their registers in LDS, then all threads sum the four rows
     // and write the result with coalesced stores.
     constexpr int HALF = NPARAM_PAD / 2;
-    float* red = reinterpret_cast<float*>(smem + BWD_OFF_IMG);              // [4][HALF], aliases the images
+    float* red = reinterpret_cast<float*>(work);                            // [4][HALF], aliases the images
     float* out = partials + (int64_t)blockIdx.x * NPARAM_PAD;
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
@@ -601,6 +620,51 @@ mlp_bwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, co
         for (int j = threadIdx.x; j < HALF; j += BWD_THREADS)
             out[h * HALF + j] = (red[j] + red[HALF + j]) + (red[2 * HALF + j] + red[3 * HALF + j]);
     }
+}
+
+template <typename TIO, bool NARROW, bool CODED = false>
+__global__ void __launch_bounds__(BWD_THREADS)
+mlp_bwd_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, const int64_t* __restrict__ ridx,
+               int64_t num_samples, int in_dim,
+               const float* __restrict__ params, const float* __restrict__ grad_rgb, const float* __restrict__ grad_density,
+               TIO* __restrict__ grad_feats, float* __restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __bf16* sw = reinterpret_cast<__bf16*>(smem);
+    float* biasv = reinterpret_cast<float*>(smem + BWD_OFF_BIASV);
+    int* flags = reinterpret_cast<int*>(smem + BWD_OFF_FLAGS);              // ready[4], done[4]
+    float* stg = reinterpret_cast<float*>(smem + BWD_OFF_IMG);              // aliases the images
+    stage_params<BWD_THREADS>(stg, params, threadIdx.x, NARROW ? in_dim : IN);
+    if (threadIdx.x < 16) flags[threadIdx.x] = 0;
+    __syncthreads();
+    stage_weights<true>(sw, stg, threadIdx.x, BWD_THREADS);
+    stage_bias_vectors(biasv, stg, threadIdx.x, BWD_THREADS);
+    LaneConst L;
+    lane_const<true>(L, sw, stg, threadIdx.x & 63, biasv);
+    __syncthreads();
+    bwd_tiles<TIO, NARROW, CODED>(L, sw, flags, smem + BWD_OFF_IMG, feats, dirs, ridx, num_samples, in_dim, grad_rgb, grad_density,
+                                  grad_feats, partials);
+}
+
+// mlp_bwd_kernel<TIO, NARROW, CODED = true> with its operands copied from the prebuilt image: LDS = [image][flags][rings].
+constexpr int BWDI_OFF_FLAGS = IMG_BYTES;
+constexpr int BWDI_OFF_WORK = BWDI_OFF_FLAGS + 64;
+constexpr int BWDI_LDS = BWDI_OFF_WORK + (BWD_LDS - BWD_OFF_IMG);
+static_assert(BWDI_LDS <= 160 * 1024, "LDS budget");
+template <typename TIO, bool NARROW>
+__global__ void __launch_bounds__(BWD_THREADS)
+mlp_bwd_img_kernel(const TIO* __restrict__ feats, const bf16x8* __restrict__ code, const int64_t* __restrict__ ridx,
+                   int64_t num_samples, int in_dim, const unsigned char* __restrict__ image, const float* __restrict__ grad_rgb,
+                   const float* __restrict__ grad_density, TIO* __restrict__ grad_feats, float* __restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int* flags = reinterpret_cast<int*>(smem + BWDI_OFF_FLAGS);
+    copy_image<BWD_THREADS, IMG_BYTES>(smem, image, threadIdx.x);
+    if (threadIdx.x < 16) flags[threadIdx.x] = 0;
+    __syncthreads();
+    LaneConst L;
+    lane_const_img(L, smem, threadIdx.x & 63);
+    const __bf16* swt = reinterpret_cast<const __bf16*>(smem + IMG_OFF_BWD) - L_FWD_END;      // swt + L_W5T = first transposed operand
+    bwd_tiles<TIO, NARROW, true>(L, swt, flags, smem + BWDI_OFF_WORK, feats, reinterpret_cast<const float*>(code), ridx, num_samples,
+                                 in_dim, grad_rgb, grad_density, grad_feats, partials);
 }
 
 int cu_count() {
@@ -645,9 +709,64 @@ int launch_bwd(const void* feats, const float* dirs, const int64_t* ridx, int64_
     return 0;
 }
 
+template <typename TIO, bool NARROW>
+int launch_fwd_img(const void* feats, const void* code, const int64_t* ridx, int64_t S, int in_dim, const void* image, float* rgb,
+                   float* density, hipStream_t st) {
+    const int64_t ntiles = (S + TS - 1) / TS;
+    const int grid = (int)min64(ceil_div64(ntiles, FWD_WAVES), (int64_t)2 * cu_count());
+    hipLaunchKernelGGL((mlp_fwd_img_kernel<TIO, NARROW>), dim3(grid), dim3(FWD_WAVES * 64), IMG_FWD_BYTES, st, (const TIO*)feats,
+                       (const bf16x8*)code, ridx, S, in_dim, (const unsigned char*)image, rgb, density);
+    return 0;
+}
+
+template <typename TIO, bool NARROW>
+int launch_bwd_img(const void* feats, const void* code, const int64_t* ridx, int64_t S, int in_dim, const void* image,
+                   const float* grad_rgb, const float* grad_density, void* grad_feats, float* partials, int* partial_rows, hipStream_t st) {
+    const size_t lds = BWDI_LDS;
+    auto kern = mlp_bwd_img_kernel<TIO, NARROW>;
+    const hipError_t e = WISP_ALLOW_LDS(kern, lds);
+    if (e != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, "nerf_mlp_bf16", hipGetErrorString(e));
+    const int64_t ntiles = (S + TS - 1) / TS;
+    const int grid = (int)min64(ceil_div64(ntiles, BWD_PAIRS), cu_count());
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_THREADS), lds, st, (const TIO*)feats, (const bf16x8*)code, ridx, S, in_dim,
+                       (const unsigned char*)image, grad_rgb, grad_density, (TIO*)grad_feats, partials);
+    *partial_rows = grid;
+    return 0;
+}
+
 }  // namespace
 
 namespace wisp_mlp {
+
+int64_t bf16_operand_image_bytes() { return IMG_BYTES; }
+
+void bf16_build_operand_image(const float* params, int in_dim, void* image, hipStream_t st) {
+    hipLaunchKernelGGL(mlp_operand_image_kernel, dim3((IMG_UNITS + 255) / 256), dim3(256), 0, st, params, in_dim, (unsigned char*)image);
+}
+
+#define WISP_MLP_IO_IMG(FN, ...)                                                                    \
+    if (in_dim == IN) switch (dtype_io) {                                                           \
+        case WISP_F32: return FN<float, false>(__VA_ARGS__);                                        \
+        case WISP_F16: return FN<__half, false>(__VA_ARGS__);                                       \
+        default: return FN<__hip_bfloat16, false>(__VA_ARGS__);                                     \
+    }                                                                                               \
+    switch (dtype_io) {                                                                             \
+        case WISP_F32: return FN<float, true>(__VA_ARGS__);                                         \
+        case WISP_F16: return FN<__half, true>(__VA_ARGS__);                                        \
+        default: return FN<__hip_bfloat16, true>(__VA_ARGS__);                                      \
+    }
+
+int bf16_forward_rays_img(const void* feats, int dtype_io, const void* code, const int64_t* ridx, int64_t S, int in_dim,
+                          const void* image, float* rgb, float* density, hipStream_t st) {
+    WISP_MLP_IO_IMG(launch_fwd_img, feats, code, ridx, S, in_dim, image, rgb, density, st)
+}
+
+int bf16_backward_rays_img(const void* feats, int dtype_io, const void* code, const int64_t* ridx, int64_t S, int in_dim,
+                           const void* image, const float* grad_rgb, const float* grad_density, void* grad_feats, float* partials,
+                           int* partial_rows, hipStream_t st) {
+    WISP_MLP_IO_IMG(launch_bwd_img, feats, code, ridx, S, in_dim, image, grad_rgb, grad_density, grad_feats, partials, partial_rows, st)
+}
+#undef WISP_MLP_IO_IMG
 
 #define WISP_MLP_IO(FN, ...)                                                                        \
     if (in_dim == IN) switch (dtype_io) {                                                           \

@@ -51,6 +51,17 @@ int bf16_backward_rays(const void* feats, int dtype_io, const void* code, const 
                        const float* params, const float* grad_rgb, const float* grad_density, void* grad_feats, float* partials,
                        int* partial_rows, hipStream_t st);
 
+// The per-ray kernels with their operands taken from an IMAGE built once from the parameters (nerf_mlp_image_dev.h) instead of
+// staged and converted by every workgroup: `image` = bf16_operand_image_bytes() bytes filled by bf16_build_operand_image (or by
+// the coded emit launch of raymarch.hip) from the parameters and in_dim the launch is for.  Same arithmetic, same results.
+int64_t bf16_operand_image_bytes();
+void bf16_build_operand_image(const float* params, int in_dim, void* image, hipStream_t st);
+int bf16_forward_rays_img(const void* feats, int dtype_io, const void* code, const int64_t* ridx, int64_t num_samples, int in_dim,
+                          const void* image, float* rgb, float* density, hipStream_t st);
+int bf16_backward_rays_img(const void* feats, int dtype_io, const void* code, const int64_t* ridx, int64_t num_samples, int in_dim,
+                           const void* image, const float* grad_rgb, const float* grad_density, void* grad_feats, float* partials,
+                           int* partial_rows, hipStream_t st);
+
 // wide decoders (hidden 128; nerf_mlp_wide.hip): bf16 compute only.  `workspace` = wide_workspace_bytes(num_samples, hidden).
 bool wide_supported(int hidden);
 int64_t wide_workspace_bytes(int64_t num_samples, int hidden);

@@ -14,6 +14,7 @@
 // Float expressions that decide integer outputs are evaluated with contraction OFF so that they match
 // oracle/raymarch.py bit for bit (every fp32 op rounded separately).
 #include "wisp_common.h"
+#include "nerf_mlp_image_dev.h"     // encode_dir, build_image_unit: the view code and the operand image of wisp_raymarch_ray_emit_coded
 
 // torch.linspace(0,1,N)[s] as evaluated by the reference's device kernel (see oracle/raymarch.py::linspace01)
 static __device__ __forceinline__ float linspace01(int s, int n, float step) {
@@ -181,15 +182,15 @@ raymarch_ray_count_kernel(const uint32_t* __restrict__ occ_bits, const uint8_t* 
     if (lane == 0) counts[r] = cnt;
 }
 
-__global__ void __launch_bounds__(256)
-raymarch_ray_emit_kernel(const float* __restrict__ origins, const float* __restrict__ dirs, int64_t num_rays,
-                         float near, float range, int n, const float* __restrict__ jitter, uint64_t seed,
-                         const uint32_t* __restrict__ hitmask, const int64_t* __restrict__ offsets,
-                         int64_t* __restrict__ ridx, float* __restrict__ samples, float* __restrict__ depth_samples,
-                         float* __restrict__ deltas, uint8_t* __restrict__ boundary, float* __restrict__ sample_dirs) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= num_rays) return;
+// One ray per wave.  CODED: lanes 0 and 1 also write the ray's view code (see raymarch_ray_emit_coded_kernel).
+template <bool CODED>
+static __device__ __forceinline__ void
+emit_ray(const float* __restrict__ origins, const float* __restrict__ dirs, int64_t r, int lane,
+         float near, float range, int n, const float* __restrict__ jitter, uint64_t seed,
+         const uint32_t* __restrict__ hitmask, const int64_t* __restrict__ offsets,
+         int64_t* __restrict__ ridx, float* __restrict__ samples, float* __restrict__ depth_samples,
+         float* __restrict__ deltas, uint8_t* __restrict__ boundary, float* __restrict__ sample_dirs,
+         bf16x8* __restrict__ dir_code) {
     // offsets, the ray and the first 64 mask words in ONE memory round trip (the ray and the words used to wait for the offsets:
     // rays without samples leave below, their 24 + 256 bytes are the price)
     const int64_t begin = offsets[r], end = offsets[r + 1];
@@ -197,6 +198,13 @@ raymarch_ray_emit_kernel(const float* __restrict__ origins, const float* __restr
     const float dx = dirs[r * 3], dy = dirs[r * 3 + 1], dz = dirs[r * 3 + 2];
     const int words0 = (n + 31) >> 5;
     const uint32_t first_words = lane < words0 ? hitmask[r * words0 + lane] : 0u;
+    if (CODED && lane < 2) {                          // every ray, the ones without samples included
+        const float d3[3] = {dx, dy, dz};
+        bf16x8 k1, k2;
+        wisp_mlp_dev::encode_dir(d3, lane, k1, k2);
+        dir_code[(r * 2 + lane) * 2] = k1;
+        dir_code[(r * 2 + lane) * 2 + 1] = k2;
+    }
     if (end == begin) return;
     const float step = n > 1 ? __fdiv_rn(1.0f, (float)(n - 1)) : 0.0f;
     const float fn = (float)n;
@@ -239,6 +247,46 @@ raymarch_ray_emit_kernel(const float* __restrict__ origins, const float* __restr
     }
 }
 
+__global__ void __launch_bounds__(256)
+raymarch_ray_emit_kernel(const float* __restrict__ origins, const float* __restrict__ dirs, int64_t num_rays,
+                         float near, float range, int n, const float* __restrict__ jitter, uint64_t seed,
+                         const uint32_t* __restrict__ hitmask, const int64_t* __restrict__ offsets,
+                         int64_t* __restrict__ ridx, float* __restrict__ samples, float* __restrict__ depth_samples,
+                         float* __restrict__ deltas, uint8_t* __restrict__ boundary, float* __restrict__ sample_dirs) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= num_rays) return;
+    emit_ray<false>(origins, dirs, r, lane, near, range, n, jitter, seed, hitmask, offsets, ridx, samples, depth_samples, deltas,
+                    boundary, sample_dirs, nullptr);
+}
+
+// The same launch also writes the decoder's per-ray view code ([ray][g][16] bf16, what dir_code_kernel of nerf_mlp_bf16.hip
+// writes from the same directions with the same encode_dir): the wave has the ray's direction in registers, and a training
+// step saves a launch of its own for a few thousand rays.  With `image` the workgroups behind the rays' build the decoder's operand
+// image (nerf_mlp_image_dev.h) from the parameters, one 16-byte unit per thread: the decoder launches of the step copy it instead of
+// converting the parameters in every workgroup.  (The optimizer launch of the previous step precedes this one in stream order.)
+__global__ void __launch_bounds__(256)
+raymarch_ray_emit_coded_kernel(const float* __restrict__ origins, const float* __restrict__ dirs, int64_t num_rays,
+                               float near, float range, int n, const float* __restrict__ jitter, uint64_t seed,
+                               const uint32_t* __restrict__ hitmask, const int64_t* __restrict__ offsets,
+                               int64_t* __restrict__ ridx, float* __restrict__ samples, float* __restrict__ depth_samples,
+                               float* __restrict__ deltas, uint8_t* __restrict__ boundary, float* __restrict__ sample_dirs,
+                               bf16x8* __restrict__ dir_code, const float* __restrict__ dec_params, int in_dim,
+                               unsigned char* __restrict__ image) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= num_rays) {
+        const int64_t ray_blocks = (num_rays + (blockDim.x >> 6) - 1) / (blockDim.x >> 6);
+        if (image && (int64_t)blockIdx.x >= ray_blocks) {
+            const int64_t u = ((int64_t)blockIdx.x - ray_blocks) * blockDim.x + threadIdx.x;
+            if (u < wisp_mlp_dev::IMG_UNITS) wisp_mlp_dev::build_image_unit(dec_params, in_dim, image, (int)u);
+        }
+        return;
+    }
+    emit_ray<true>(origins, dirs, r, lane, near, range, n, jitter, seed, hitmask, offsets, ridx, samples, depth_samples, deltas,
+                   boundary, sample_dirs, dir_code);
+}
+
 extern "C" int wisp_raymarch_ray_count(const uint32_t* occ_bits, const uint8_t* octree, const int32_t* exsum,
                                        const float* origins, const float* dirs, int64_t num_rays, float near,
                                        float range, int num_samples, int level, const float* jitter, uint64_t seed,
@@ -268,6 +316,29 @@ extern "C" int wisp_raymarch_ray_emit(const float* origins, const float* dirs, i
     hipLaunchKernelGGL(raymarch_ray_emit_kernel, dim3((unsigned)ceil_div64(num_rays, RAY_WAVES)), dim3(64 * RAY_WAVES), 0,
                        (hipStream_t)stream, origins, dirs, num_rays, near, range, num_samples, jitter, seed, hitmask,
                        offsets, ridx, samples, depth_samples, deltas, boundary, sample_dirs);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
+extern "C" int wisp_raymarch_ray_emit_coded(const float* origins, const float* dirs, int64_t num_rays, float near, float range,
+                                            int num_samples, const float* jitter, uint64_t seed, const uint32_t* hitmask,
+                                            const int64_t* offsets, int64_t* ridx, float* samples, float* depth_samples,
+                                            float* deltas, uint8_t* boundary, float* sample_dirs, int view_freqs, void* dir_code,
+                                            const float* dec_params, int in_dim, int hidden, void* operand_image,
+                                            wisp_stream_t stream) {
+    WISP_REQUIRE(num_rays >= 0 && num_samples >= 1, "bad sizes");
+    WISP_REQUIRE(view_freqs == wisp_mlp::NF, "this build supports view_freqs=4");
+    if (operand_image && (hidden != wisp_mlp::H || in_dim < 1 || in_dim > wisp_mlp::IN))
+        return wisp_fail(WISP_ERR_UNSUPPORTED, "nerf_mlp_rays", "operand images: 1 <= in_dim <= 32, hidden 64");
+    WISP_REQUIRE(!operand_image || dec_params, "operand_image without dec_params");
+    if (num_rays == 0 && !operand_image) return WISP_OK;
+    WISP_REQUIRE(num_rays == 0 || (origins && dirs && hitmask && offsets && dir_code), "null pointer");
+    const int64_t ray_blocks = ceil_div64(num_rays, RAY_WAVES);
+    const int64_t image_blocks = operand_image ? ceil_div64(wisp_mlp_dev::IMG_UNITS, 64 * RAY_WAVES) : 0;
+    hipLaunchKernelGGL(raymarch_ray_emit_coded_kernel, dim3((unsigned)(ray_blocks + image_blocks)), dim3(64 * RAY_WAVES), 0,
+                       (hipStream_t)stream, origins, dirs, num_rays, near, range, num_samples, jitter, seed, hitmask,
+                       offsets, ridx, samples, depth_samples, deltas, boundary, sample_dirs, reinterpret_cast<bf16x8*>(dir_code),
+                       dec_params, in_dim, static_cast<unsigned char*>(operand_image));
     WISP_CHECK_LAUNCH();
     return WISP_OK;
 }

@@ -1,7 +1,7 @@
 // One optimisation step of the nerf_hash.yaml training shape issued from native code: every launch of
 //   MultiviewTrainer.step (wisp/trainers/multiview_trainer.py:111-180) -> PackedRFTracer.trace (packed_rf_tracer.py:84-181) ->
 //   HashGrid.interpolate + NeuralRadianceField.rgba (nerf.py:219-264) -> compositing + loss -> backward -> AdamW (base_trainer.py:205-246)
-// - ray emit, the next batch's occupancy count + scan + size read-back, hash-grid lookup, view code, decoder forward, compositing +
+// - ray emit (with the per-ray view code), the next batch's occupancy count + scan + size read-back, hash-grid lookup, decoder forward, compositing +
 // loss + its backward, decoder backward, hash-grid backward (with the table's AdamW folded in), AdamW of everything else - in ONE
 // call across the language boundary.  No kernel lives here: the function calls the library's own C-ABI entry points in the order
 // wisp/trainers/multiview_trainer.py::_DirectNeRFStep.run issues them, on buffers carved out of one caller-owned workspace, so the
@@ -42,7 +42,7 @@ struct MarchSlot {
 
 struct Layout {
     int64_t hitmask[2], counts[2], offsets[2], scan_ws[2];
-    int64_t ridx, samples, depth, deltas, boundary, feats, dir_code, color, density, g_color, g_density, g_feats, comp_ws, loss, mlp_ws;
+    int64_t ridx, samples, depth, deltas, boundary, feats, dir_code, image, color, density, g_color, g_density, g_feats, comp_ws, loss, mlp_ws;
     int64_t comp_ws_floats, mlp_ws_bytes, total;
 };
 
@@ -70,6 +70,8 @@ static Layout layout_of(const wisp_nerf_step_config& c) {
     L.boundary = take(S);
     L.feats = take(S * row);
     L.dir_code = take(R * 32 * 2);
+    const int64_t image_bytes = wisp_nerf_mlp_operand_image_bytes(c.hidden);      // (<= 0: no image kernels for this shape)
+    L.image = take(image_bytes > 0 ? image_bytes : 0);
     L.color = take(S * 12);
     L.density = take(S * 4);
     L.g_color = take(S * 12);
@@ -278,8 +280,13 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
 
     // ---- this batch's samples; the NEXT batch's occupancy test right behind them (its size read-back is long done when the next
     //      step asks for it)
-    NS_CALL(wisp_raymarch_ray_emit(m.origins, m.dirs, R, c.near, c.range, c.num_samples, nullptr, m.seed, m.hitmask, m.offsets, ridx,
-                                   samples, depth, deltas, boundary, nullptr, st));
+    //      The emit launch writes the decoder's per-ray view code too (no launch of wisp_nerf_mlp_dir_code's) and builds the decoder's
+    //      operand image from the parameters as the previous step's optimizer launch left them.  The image is made and used inside
+    //      this call only, so it can never be older than the parameters it stands for.
+    void* image = wisp_nerf_mlp_operand_image_bytes(c.hidden) > 0 ? at<void>(s, s->lay.image) : nullptr;
+    NS_CALL(wisp_raymarch_ray_emit_coded(m.origins, m.dirs, R, c.near, c.range, c.num_samples, nullptr, m.seed, m.hitmask, m.offsets,
+                                         ridx, samples, depth, deltas, boundary, nullptr, c.view_freqs, code,
+                                         image ? c.dec_params : nullptr, c.in_dim, c.hidden, image, st));
     if (next_origins) NS_CALL(do_count(s, slot ^ 1, next_origins, next_dirs, next_num_rays, next_seed, st));
 
     // ---- forward
@@ -287,16 +294,23 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
     NS_CALL(wisp_hashgrid_interpolate_fwd(samples, S, 3, c.table_lookup, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
                                           c.num_lods, c.bitwidth, c.zero_from_col, feats, st));
     NS_MARK(1);
-    NS_CALL(wisp_nerf_mlp_dir_code(m.dirs, R, c.view_freqs, code, st));
     NS_MARK(2);
-    NS_CALL(wisp_nerf_mlp_fwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, color, density, st));
+    if (image)
+        NS_CALL(wisp_nerf_mlp_fwd_rays_img(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, image, color,
+                                           density, st));
+    else
+        NS_CALL(wisp_nerf_mlp_fwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, color, density, st));
     NS_MARK(3);
     NS_CALL(wisp_composite_loss(color, density, deltas, m.offsets, R, S, c.bg, gts, c.loss_kind, g_color, g_density, nullptr, loss_slot,
                                 at<float>(s, s->lay.comp_ws), s->lay.comp_ws_floats, st));
     // ---- backward
     NS_MARK(4);
-    NS_CALL(wisp_nerf_mlp_bwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, g_color, g_density,
-                                   g_feats, c.dec_grad, at<float>(s, s->lay.mlp_ws), s->lay.mlp_ws_bytes, st));
+    if (image)
+        NS_CALL(wisp_nerf_mlp_bwd_rays_img(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, image, g_color,
+                                           g_density, g_feats, c.dec_grad, at<float>(s, s->lay.mlp_ws), s->lay.mlp_ws_bytes, st));
+    else
+        NS_CALL(wisp_nerf_mlp_bwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, g_color, g_density,
+                                       g_feats, c.dec_grad, at<float>(s, s->lay.mlp_ws), s->lay.mlp_ws_bytes, st));
     NS_MARK(5);
     int64_t covered[16] = {0};
     const bool fold = hp->optimizer == 2 && c.table_param && c.table_exp_avg && c.table_exp_avg_sq;

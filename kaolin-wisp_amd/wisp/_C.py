@@ -68,6 +68,8 @@ SIGNATURES = {
     "wisp_boundary_pack_starts": [c_vp, c_i64, c_vp, c_vp, c_vp],
     "wisp_raymarch_ray_count": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_i32, c_i32, c_vp, c_u64, c_vp, c_i32, c_vp, c_vp, c_vp],
     "wisp_raymarch_ray_emit": [c_vp, c_vp, c_i64, c_f32, c_f32, c_i32, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "wisp_raymarch_ray_emit_coded": [c_vp, c_vp, c_i64, c_f32, c_f32, c_i32, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                     c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     "wisp_raymarch_voxel_emit": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_raymarch_uniform_count": [c_vp, c_i64, c_f32, c_vp, c_vp],
     "wisp_spc_mask_from_points": [c_vp, c_i64, c_i32, c_vp, c_vp],
@@ -115,6 +117,10 @@ SIGNATURES = {
     "wisp_nerf_mlp_fwd": [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_bwd": [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_nerf_mlp_dir_code": [c_vp, c_i64, c_i32, c_vp, c_vp],
+    "wisp_nerf_mlp_operand_image_bytes": [c_i32],
+    "wisp_nerf_mlp_build_operand_image": [c_vp, c_i32, c_i32, c_vp, c_vp],
+    "wisp_nerf_mlp_fwd_rays_img": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "wisp_nerf_mlp_bwd_rays_img": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_nerf_mlp_fwd_rays": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_bwd_rays": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_nerf_mlp_bwd_workspace_bytes": [c_i64, c_i32],
@@ -1158,15 +1164,29 @@ def _total(st):
     return pending.take()
 
 
-def raymarch_ray_finish(st, with_dirs=False):
+def raymarch_ray_finish(st, with_dirs=False, with_code=False, view_freqs=4, image_of=None):
     """Second half: read the sample count back (the reference syncs here too: nonzero, octree_as.py:288), allocate and
     emit.  Returns (ridx, samples, depth, deltas, boundary, ray_offsets) - plus the per-sample view directions
-    dirs[ridx] ([S,3], what packed_rf_tracer.py:120 gathers) when with_dirs is set."""
+    dirs[ridx] ([S,3], what packed_rf_tracer.py:120 gathers) when with_dirs is set, plus the per-ray view code of
+    nerf_mlp_dir_code ([R,32] bf16, written by the emit launch itself: wisp_raymarch_ray_emit_coded) when with_code is, plus the
+    decoder's operand image of image_of = (params, in_dim, hidden) (nerf_mlp_operand_image, built by the same launch) when given."""
     origins, offsets = st["origins"], st["offsets"]
     R, dev = origins.shape[0], origins.device
     S = _total(st)
     ridx, samples, depth, deltas, boundary = _alloc_samples(S, dev)
     sample_dirs = torch.empty(S, 3, dtype=torch.float32, device=dev) if with_dirs else None
+    if with_code or image_of is not None:
+        code = torch.empty(R, 32, dtype=torch.bfloat16, device=dev)
+        params, in_dim, hidden, image = None, 0, 0, None
+        if image_of is not None:
+            params, in_dim, hidden = _need(image_of[0], torch.float32, "params"), int(image_of[1]), int(image_of[2])
+            image = _operand_image_buffer(hidden, dev)
+        _check(lib.wisp_raymarch_ray_emit_coded(_p(origins), _p(st["dirs"]), R, st["near32"], st["range32"], st["num_samples"],
+                                                _p(st["jitter"]), st["seed"], _p(st["hitmask"]), _p(offsets), _p(ridx), _p(samples),
+                                                _p(depth), _p(deltas), _p(boundary), _p(sample_dirs), view_freqs, _p(code),
+                                                _p(params), in_dim, hidden, _p(image), _stream()), "raymarch_ray_emit_coded")
+        out = (ridx, samples, depth, deltas, boundary, offsets)
+        return out + ((sample_dirs,) if with_dirs else ()) + (code,) + ((image,) if image_of is not None else ())
     if S:
         _check(lib.wisp_raymarch_ray_emit(_p(origins), _p(st["dirs"]), R, st["near32"], st["range32"], st["num_samples"],
                                           _p(st["jitter"]), st["seed"], _p(st["hitmask"]), _p(offsets), _p(ridx), _p(samples),
@@ -1872,7 +1892,8 @@ def _check_decoder_shapes(feats, params, in_dim, hidden, view_freqs):
 
 def nerf_mlp_forward(feats, dirs, params, in_dim, hidden, view_freqs, compute_bf16, ray_code=None):
     """(rgb [S,3], density [S,1]) = fused density + colour decoders (nerf.py:245-264).
-    ray_code = (ridx int64 [S], code from nerf_mlp_dir_code) replaces the per-sample `dirs` (then None)."""
+    ray_code = (ridx int64 [S], code from nerf_mlp_dir_code) replaces the per-sample `dirs` (then None); a third element, the
+    image of nerf_mlp_operand_image(params, in_dim, hidden), selects the kernels that copy their operands from it."""
     feats = _need(feats, None, "feats")
     params = _need(params, torch.float32, "params")
     _check_decoder_shapes(feats, params, in_dim, hidden, view_freqs)
@@ -1886,8 +1907,13 @@ def nerf_mlp_forward(feats, dirs, params, in_dim, hidden, view_freqs, compute_bf
         if ridx.shape[0] != S:
             raise ValueError("ridx must have one entry per sample")
         with _timed("nerf_mlp_fwd", S):
-            _check(lib.wisp_nerf_mlp_fwd_rays(_p(feats), _DTYPE_CODE[feats.dtype], _p(code), _p(ridx), S, in_dim, hidden, view_freqs,
-                                              _p(params), _p(rgb), _p(density), _stream()), "nerf_mlp_fwd_rays")
+            if len(ray_code) > 2:
+                image = _need(ray_code[2], torch.uint8, "operand image")
+                _check(lib.wisp_nerf_mlp_fwd_rays_img(_p(feats), _DTYPE_CODE[feats.dtype], _p(code), _p(ridx), S, in_dim, hidden, view_freqs,
+                                                      _p(params), _p(image), _p(rgb), _p(density), _stream()), "nerf_mlp_fwd_rays_img")
+            else:
+                _check(lib.wisp_nerf_mlp_fwd_rays(_p(feats), _DTYPE_CODE[feats.dtype], _p(code), _p(ridx), S, in_dim, hidden, view_freqs,
+                                                  _p(params), _p(rgb), _p(density), _stream()), "nerf_mlp_fwd_rays")
         return rgb, density
     dirs = _need(dirs, torch.float32, "dirs")
     with _timed("nerf_mlp_fwd", S):
@@ -1903,6 +1929,23 @@ def nerf_mlp_dir_code(ray_dirs, view_freqs=4):
     code = torch.empty(R, 32, dtype=torch.bfloat16, device=ray_dirs.device)
     _check(lib.wisp_nerf_mlp_dir_code(_p(ray_dirs), R, view_freqs, _p(code), _stream()), "nerf_mlp_dir_code")
     return code
+
+
+def _operand_image_buffer(hidden, dev):
+    n = int(lib.wisp_nerf_mlp_operand_image_bytes(hidden))
+    if n <= 0:
+        raise RuntimeError(f"nerf_mlp_operand_image: {last_error()}")
+    return torch.empty(n, dtype=torch.uint8, device=dev)
+
+
+def nerf_mlp_operand_image(params, in_dim, hidden=64):
+    """The bf16 decoder's operands as the kernels want them in LDS, built once from the packed parameters (uint8 tensor, opaque):
+    nerf_mlp_forward / nerf_mlp_backward(..., ray_code=(ridx, code, image)) copy it instead of converting `params` in every
+    workgroup.  It stands for `params` as they are NOW: build it again after every change of them."""
+    params = _need(params, torch.float32, "params")
+    image = _operand_image_buffer(hidden, params.device)
+    _check(lib.wisp_nerf_mlp_build_operand_image(_p(params), in_dim, hidden, _p(image), _stream()), "nerf_mlp_build_operand_image")
+    return image
 
 
 def nerf_mlp_rays_supported(feats_dtype, in_dim, hidden, view_freqs, compute_bf16):
@@ -1953,9 +1996,15 @@ def nerf_mlp_backward(feats, dirs, params, grad_rgb, grad_density, in_dim, hidde
         if ridx.shape[0] != S:
             raise ValueError("ridx must have one entry per sample")
         with _timed("nerf_mlp_bwd", S):
-            _check(lib.wisp_nerf_mlp_bwd_rays(_p(feats), _DTYPE_CODE[feats.dtype], _p(code), _p(ridx), S, in_dim, hidden, view_freqs,
-                                              _p(params), _p(grad_rgb), _p(grad_density), _p(grad_feats), _p(grad_params), _p(ws),
-                                              ws.numel() * 4, _stream()), "nerf_mlp_bwd_rays")
+            if len(ray_code) > 2:
+                image = _need(ray_code[2], torch.uint8, "operand image")
+                _check(lib.wisp_nerf_mlp_bwd_rays_img(_p(feats), _DTYPE_CODE[feats.dtype], _p(code), _p(ridx), S, in_dim, hidden, view_freqs,
+                                                      _p(params), _p(image), _p(grad_rgb), _p(grad_density), _p(grad_feats),
+                                                      _p(grad_params), _p(ws), ws.numel() * 4, _stream()), "nerf_mlp_bwd_rays_img")
+            else:
+                _check(lib.wisp_nerf_mlp_bwd_rays(_p(feats), _DTYPE_CODE[feats.dtype], _p(code), _p(ridx), S, in_dim, hidden, view_freqs,
+                                                  _p(params), _p(grad_rgb), _p(grad_density), _p(grad_feats), _p(grad_params), _p(ws),
+                                                  ws.numel() * 4, _stream()), "nerf_mlp_bwd_rays")
         return grad_feats, grad_params
     with _timed("nerf_mlp_bwd", S):
         _check(lib.wisp_nerf_mlp_bwd(_p(feats), _DTYPE_CODE[feats.dtype], _p(dirs), S, in_dim, hidden, view_freqs, _p(params),
