@@ -633,6 +633,339 @@ composite_loss_kernel(const float* __restrict__ color, const float* __restrict__
     if (lane == 0) partial[v] = lacc;
 }
 
+// ---- the same pass with long rays split over the four waves of their workgroup ------------------------------------------
+// composite_loss_kernel spends its launch in its longest ray: a ray of n > 64 samples walks ceil(n / 64) chunks three times, each
+// round a dependent load -> scan -> exp chain (36 rounds for the 718-sample ray of a 2^18 batch, while 79 % of the rays are
+// empty).  Here a workgroup still holds four consecutive rays, one per wave, and a wave whose ray has at most 64 samples (or
+// more than 256 K samples) does what it does there; then the workgroup goes over its long rays one at a time, chunk c on wave c % 4,
+// every chunk in registers (K per wave), every load of the ray issued at once:
+//   1  load; tau, in-chunk scan, chunk total -> LDS                                                                 | barrier
+//   2  carry = the chunk totals added in chunk order from 0 (the adds of `carry +=`); T, et, w; w and colour -> LDS | barrier
+//   3  wave q adds sum q (r, g, b, alpha) per lane in chunk order, then over the lanes; -> LDS                      | barrier
+//   4  every wave: rgb, loss terms, g (same inputs, same code: no broadcast); G of its chunks; scan of G w, totals -> LDS | barrier
+//   5  every wave: total of G w per lane in chunk order; gcarry like carry; the gradients from registers
+// Only workgroup barriers and LDS; every wave reaches each barrier once per long ray, and which rays are long is decided from the
+// same four offset pairs by every wave, rays behind the last one count as empty.
+// The results are those of composite_loss_kernel bit for bit: every sum keeps its order, and every product-sum is written out
+// as that kernel's code object evaluates it (fmaf where it contracts, separate roundings where it does not - it contracts
+// sr and sg but not sb, G differently in each of its three places, and the first step of the scan of G w with the product).
+#define WISP_DPP_ADD(V, CTRL, RMASK)                                                                                  \
+    V = V + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, V), CTRL, RMASK, 0xf, false))
+// inclusive scan of a * b whose first step is fma(a, b, shr1(a * b))
+static __device__ __forceinline__ float wave_incl_scan_prod_f(float a, float b) {
+#pragma clang fp contract(off)
+    const float p = a * b;
+    float v = fmaf(a, b, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p), 0x111, 0xf, 0xf, false)));
+    WISP_DPP_ADD(v, 0x112, 0xf);
+    WISP_DPP_ADD(v, 0x114, 0xf);
+    WISP_DPP_ADD(v, 0x118, 0xf);
+    WISP_DPP_ADD(v, 0x142, 0xa);
+    WISP_DPP_ADD(v, 0x143, 0xc);
+    return v;
+}
+#undef WISP_DPP_ADD
+
+// rgb, d loss / d rgb and the ray's loss term from its four sums
+static __device__ __forceinline__ float ray_loss_terms(float sr, float sg, float sb, float sa, const Bg& bg, float gt0, float gt1,
+                                                       float gt2, int kind, float inv_n, float (&rgb)[3], float (&g)[3]) {
+#pragma clang fp contract(off)
+    const float om = 1.0f - sa;
+    rgb[0] = fmaf(bg.r, om, sr); rgb[1] = fmaf(bg.g, om, sg); rgb[2] = fmaf(bg.b, om, sb);
+    const float gtc[3] = {gt0, gt1, gt2};
+    float lsum[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float x = rgb[c] - gtc[c];
+        float l, d;
+        if (kind == 0) { const float a = fabsf(x); const float h = 0.5f * x; l = a < 1.0f ? h * x : a - 0.5f; d = fminf(fmaxf(x, -1.0f), 1.0f); }
+        else if (kind == 1) { l = x * x; d = 2.0f * x; }
+        else { l = fabsf(x); d = (x > 0.0f) ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+        lsum[c] = l;
+        g[c] = d * inv_n;
+    }
+    return (lsum[0] + lsum[1]) + lsum[2];
+}
+
+// one ray on one wave, as composite_loss_kernel does it: at most 64 samples out of registers, more in three passes
+static __device__ __forceinline__ float composite_ray_serial(const float* __restrict__ color, const float* __restrict__ density,
+                                                             const float* __restrict__ deltas, int64_t b, int64_t e, int64_t r,
+                                                             int lane, const Bg& bg, const float* __restrict__ gt, int kind,
+                                                             float inv_n, float* __restrict__ grad_color,
+                                                             float* __restrict__ grad_density, float* __restrict__ out_rgb) {
+#pragma clang fp contract(off)
+    const float gt0 = gt[r * 3], gt1 = gt[r * 3 + 1], gt2 = gt[r * 3 + 2];
+    const bool single = e - b <= 64;
+    float carry = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;
+    float dl = 0.0f, T = 0.0f, et = 0.0f, w = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+        const int64_t i = k0 + lane;
+        const bool live = i < e;
+        dl = live ? deltas[i] : 0.0f;
+        const float dn = live ? density[i] : 0.0f;
+        c0 = live ? color[i * 3] : 0.0f; c1 = live ? color[i * 3 + 1] : 0.0f; c2 = live ? color[i * 3 + 2] : 0.0f;
+        const float tau = live ? dn * dl : 0.0f;
+        const float inc = wave_incl_scan_f(tau, lane);
+        const float excl = carry + (inc - tau);
+        carry = carry + wave_last_f(inc);
+        T = 0.0f; et = 0.0f; w = 0.0f;
+        if (live) {
+            T = expf(-excl); et = expf(-tau);
+            w = (1.0f - et) * T;
+            sr = fmaf(c0, w, sr); sg = fmaf(c1, w, sg);
+            const float pb = c2 * w;
+            sb = sb + pb;
+            sa = sa + w;
+        }
+    }
+    if (b < e) { sr = wave_sum_f(sr); sg = wave_sum_f(sg); sb = wave_sum_f(sb); sa = wave_sum_f(sa); }
+    float rgb[3], g[3];
+    const float term = ray_loss_terms(sr, sg, sb, sa, bg, gt0, gt1, gt2, kind, inv_n, rgb, g);
+    if (out_rgb && lane == 0) { out_rgb[r * 3] = rgb[0]; out_rgb[r * 3 + 1] = rgb[1]; out_rgb[r * 3 + 2] = rgb[2]; }
+    if (b == e) return term;
+    const float gr = g[0], gg = g[1], gb = g[2];
+    if (single) {
+        const int64_t i = b + lane;
+        const bool live = i < e;
+        const float a0 = c0 - bg.r, a1 = c1 - bg.g, a2 = c2 - bg.b;
+        const float G = live ? fmaf(a2, gb, fmaf(a0, gr, a1 * gg)) : 0.0f;
+        const float ginc = wave_incl_scan_prod_f(w, G);
+        const float tot = wave_last_f(ginc);
+        const float suffix = tot - ginc;
+        if (live) {
+            grad_color[i * 3] = w * gr; grad_color[i * 3 + 1] = w * gg; grad_color[i * 3 + 2] = w * gb;
+            const float tg = T * G;
+            grad_density[i] = fmaf(et, tg, -suffix) * dl;
+        }
+        return term;
+    }
+    carry = 0.0f;
+    float tot = 0.0f;
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+        const int64_t i = k0 + lane;
+        const bool live = i < e;
+        const float tau = live ? density[i] * deltas[i] : 0.0f;
+        const float inc = wave_incl_scan_f(tau, lane);
+        const float excl = carry + (inc - tau);
+        carry = carry + wave_last_f(inc);
+        if (live) {
+            const float ww = (1.0f - expf(-tau)) * expf(-excl);
+            const float p0 = gr * (color[i * 3] - bg.r), p1 = gg * (color[i * 3 + 1] - bg.g), p2 = gb * (color[i * 3 + 2] - bg.b);
+            const float G = (p0 + p1) + p2;
+            tot = fmaf(ww, G, tot);
+        }
+    }
+    tot = wave_sum_f(tot);
+    carry = 0.0f;
+    float gcarry = 0.0f;
+    for (int64_t k0 = b; k0 < e; k0 += 64) {
+        const int64_t i = k0 + lane;
+        const bool live = i < e;
+        const float dd = live ? deltas[i] : 0.0f;
+        const float tau = live ? density[i] * dd : 0.0f;
+        const float inc = wave_incl_scan_f(tau, lane);
+        const float excl = carry + (inc - tau);
+        carry = carry + wave_last_f(inc);
+        float TT = 0.0f, ee = 0.0f, ww = 0.0f, G = 0.0f;
+        if (live) {
+            TT = expf(-excl); ee = expf(-tau); ww = (1.0f - ee) * TT;
+            const float p0 = gr * (color[i * 3] - bg.r), p2 = gb * (color[i * 3 + 2] - bg.b);
+            G = fmaf(gg, color[i * 3 + 1] - bg.g, p0) + p2;
+        }
+        const float ginc = wave_incl_scan_prod_f(ww, G);
+        const float suffix = tot - (gcarry + ginc);
+        gcarry = gcarry + wave_last_f(ginc);
+        if (live) {
+            grad_color[i * 3] = ww * gr; grad_color[i * 3 + 1] = ww * gg; grad_color[i * 3 + 2] = ww * gb;
+            const float tg = TT * G;
+            grad_density[i] = fmaf(ee, tg, -suffix) * dd;
+        }
+    }
+    return term;
+}
+
+// running sum of the chunk totals tot[0 .. nch) in chunk order; out[k] = the sum in front of chunk wv + 4 k.  Lane c fetches
+// tot[c] once and the adds take their operand with v_readlane: a loop of LDS reads, each behind the add before it, cost 75 ns per
+// chunk - more than everything else a long ray does here.  (Chunks behind the last add +0.0 to a sum nothing uses.)
+template <int K>
+static __device__ __forceinline__ void chunk_carries(const float* tot, int nch, int wv, int lane, float (&out)[K]) {
+#pragma clang fp contract(off)
+    const float mine = lane < nch ? tot[lane] : 0.0f;
+    float run = 0.0f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        out[k] = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (q == wv) out[k] = run;
+            run = run + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), 4 * k + q));
+        }
+    }
+}
+
+// per-lane accumulation over the chunks in chunk order, four chunks' LDS reads in flight:
+// MODE 0  acc = fma(a, b, acc)     1  acc = acc + a * b     2  acc = acc + b
+template <int MODE>
+static __device__ __forceinline__ float chunk_accumulate(const float* sa, const float* sb, int nch, int lane) {
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+    for (int cb = 0; cb < nch; cb += 4) {                     // (nch <= 4 K: cb + 3 stays inside the arrays)
+        float a[4], b[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { a[q] = MODE == 2 ? 0.0f : sa[(cb + q) * 64 + lane]; b[q] = sb[(cb + q) * 64 + lane]; }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (cb + q < nch) {                               // wave-uniform
+                if (MODE == 0) acc = fmaf(a[q], b[q], acc);
+                else if (MODE == 1) { const float p = a[q] * b[q]; acc = acc + p; }
+                else acc = acc + b[q];
+            }
+        }
+    }
+    return acc;
+}
+
+template <int K>
+// K chunks of a ray per wave in registers.  K = 4 (rays of up to 1 024 samples; the longest of a 2^18 batch has 718) compiles to
+// 80 VGPRs, 16 KB of LDS and no scratch: six waves per SIMD, all workgroups of a 2^18 batch resident at once.  K = 8 (2 048 samples,
+// 155 VGPRs, 32 KB, three waves per SIMD) was measured and is slower than the kernel this one replaces (25.9 against 18.9 us,
+// profiles/long_rays_ab.txt): every long ray pays for the unrolled chunk slots it does not use.  A longer ray takes the three
+// passes on its own wave.
+__global__ void __launch_bounds__(256, 5)
+composite_loss_split_kernel(const float* __restrict__ color, const float* __restrict__ density, const float* __restrict__ deltas,
+                            const int64_t* __restrict__ offsets, int64_t num_rays, Bg bg, const float* __restrict__ gt, int kind,
+                            float inv_n, float* __restrict__ grad_color, float* __restrict__ grad_density,
+                            float* __restrict__ out_rgb, float* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int NCH = 4 * K;                                // chunks of the longest ray of the split path
+    __shared__ float s_w[NCH * 64];                           // [chunk][lane]: w
+    __shared__ float s_c[3][NCH * 64];                        // [chunk][lane]: colour; behind barrier 3, s_c[0] = G of the total
+    __shared__ float s_tot[NCH], s_gtot[NCH], s_sum[4];
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * 4;
+    // the four offset pairs of the workgroup, read by every wave: the same values, the same decisions
+    int64_t ob[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) ob[j] = offsets[r0 + j < num_rays ? r0 + j : num_rays];
+    {
+        const int64_t r = r0 + wv;
+        if (r < num_rays) {                                   // (no barrier in here)
+            const int64_t len = ob[wv + 1 < 5 ? wv + 1 : 4] - ob[wv];
+            const int64_t b = wv == 0 ? ob[0] : wv == 1 ? ob[1] : wv == 2 ? ob[2] : ob[3];
+            if (len <= 64 || len > 64 * NCH) {
+                float lacc = 0.0f;
+                lacc = lacc + composite_ray_serial(color, density, deltas, b, b + len, r, lane, bg, gt, kind, inv_n, grad_color,
+                                                   grad_density, out_rgb);
+                if (lane == 0) partial[r] = lacc;
+            }
+        }
+    }
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+        const int64_t b = j == 0 ? ob[0] : j == 1 ? ob[1] : j == 2 ? ob[2] : ob[3];
+        const int64_t e = j == 0 ? ob[1] : j == 1 ? ob[2] : j == 2 ? ob[3] : ob[4];
+        const int64_t len = e - b;
+        if (len <= 64 || len > 64 * NCH) continue;            // workgroup-uniform
+        const int64_t r = r0 + j;                             // < num_rays: a ray behind the last one has length 0
+        const int nch = (int)((len + 63) >> 6);
+        const float gt0 = gt[r * 3], gt1 = gt[r * 3 + 1], gt2 = gt[r * 3 + 2];
+        float dl[K], tau[K], inc[K], c0[K], c1[K], c2[K];
+        // 1: every load of the wave's chunks first, then the scans
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int64_t i = b + (int64_t)(wv + 4 * k) * 64 + lane;
+            const bool live = i < e;
+            dl[k] = live ? deltas[i] : 0.0f;
+            tau[k] = live ? density[i] : 0.0f;
+            c0[k] = live ? color[i * 3] : 0.0f; c1[k] = live ? color[i * 3 + 1] : 0.0f; c2[k] = live ? color[i * 3 + 2] : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int c = wv + 4 * k;
+            const bool live = b + (int64_t)c * 64 + lane < e;
+            tau[k] = live ? tau[k] * dl[k] : 0.0f;
+            inc[k] = wave_incl_scan_f(tau[k], lane);
+            if (c < nch && lane == 0) s_tot[c] = wave_last_f(inc[k]);
+        }
+        __syncthreads();
+        // 2
+        float T[K], et[K], w[K];
+        {
+            float carry[K];
+            chunk_carries<K>(s_tot, nch, wv, lane, carry);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int c = wv + 4 * k;
+                const bool live = b + (int64_t)c * 64 + lane < e;
+                const float excl = carry[k] + (inc[k] - tau[k]);
+                T[k] = 0.0f; et[k] = 0.0f; w[k] = 0.0f;
+                if (live) {
+                    T[k] = expf(-excl); et[k] = expf(-tau[k]);
+                    w[k] = (1.0f - et[k]) * T[k];
+                }
+                if (c < nch) {
+                    s_w[c * 64 + lane] = w[k];
+                    s_c[0][c * 64 + lane] = c0[k]; s_c[1][c * 64 + lane] = c1[k]; s_c[2][c * 64 + lane] = c2[k];
+                }
+            }
+        }
+        __syncthreads();
+        // 3: wave 0 red, 1 green, 2 blue (not contracted), 3 alpha
+        {
+            float acc;
+            if (wv == 0)      acc = chunk_accumulate<0>(s_c[0], s_w, nch, lane);
+            else if (wv == 1) acc = chunk_accumulate<0>(s_c[1], s_w, nch, lane);
+            else if (wv == 2) acc = chunk_accumulate<1>(s_c[2], s_w, nch, lane);
+            else              acc = chunk_accumulate<2>(s_w, s_w, nch, lane);
+            acc = wave_sum_f(acc);
+            if (lane == 0) s_sum[wv] = acc;
+        }
+        __syncthreads();
+        // 4
+        float rgb[3], g[3];
+        const float term = ray_loss_terms(s_sum[0], s_sum[1], s_sum[2], s_sum[3], bg, gt0, gt1, gt2, kind, inv_n, rgb, g);
+        if (wv == 0 && lane == 0) {
+            if (out_rgb) { out_rgb[r * 3] = rgb[0]; out_rgb[r * 3 + 1] = rgb[1]; out_rgb[r * 3 + 2] = rgb[2]; }
+            float lacc = 0.0f;
+            lacc = lacc + term;
+            partial[r] = lacc;
+        }
+        const float gr = g[0], gg = g[1], gb = g[2];
+        float G[K], ginc[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int c = wv + 4 * k;
+            const bool live = b + (int64_t)c * 64 + lane < e;
+            const int at = (c < nch ? c : 0) * 64 + lane;                        // the wave's own colours, back from LDS
+            const float a0 = s_c[0][at] - bg.r, a1 = s_c[1][at] - bg.g, a2 = s_c[2][at] - bg.b;
+            const float p0 = gr * a0, p1 = gg * a1, p2 = gb * a2;
+            const float Gt = live ? (p0 + p1) + p2 : 0.0f;                       // G as the pass of the total rounds it
+            G[k] = live ? fmaf(gg, a1, p0) + p2 : 0.0f;                          // G as the pass of the gradients rounds it
+            ginc[k] = wave_incl_scan_prod_f(w[k], G[k]);
+            if (c < nch) {
+                s_c[0][c * 64 + lane] = Gt;
+                if (lane == 0) s_gtot[c] = wave_last_f(ginc[k]);
+            }
+        }
+        __syncthreads();
+        // 5
+        const float tot = wave_sum_f(chunk_accumulate<0>(s_w, s_c[0], nch, lane));
+        float gcarry[K];
+        chunk_carries<K>(s_gtot, nch, wv, lane, gcarry);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int64_t i = b + (int64_t)(wv + 4 * k) * 64 + lane;
+            if (i < e) {
+                const float suffix = tot - (gcarry[k] + ginc[k]);
+                grad_color[i * 3] = w[k] * gr; grad_color[i * 3 + 1] = w[k] * gg; grad_color[i * 3 + 2] = w[k] * gb;
+                const float tg = T[k] * G[k];
+                grad_density[i] = fmaf(et[k], tg, -suffix) * dl[k];
+            }
+        }
+        // (the next long ray writes s_tot in front of its first barrier, s_w / s_c / s_sum / s_gtot behind it: nothing this ray still reads)
+    }
+}
+
 extern "C" int wisp_composite_loss(const float* color, const float* density, const float* deltas, const int64_t* ray_offsets,
                                    int64_t num_rays, int64_t num_samples, const float* bg, const float* gt, int kind,
                                    float* grad_color, float* grad_density, float* out_rgb, float* loss, float* workspace,
@@ -646,7 +979,13 @@ extern "C" int wisp_composite_loss(const float* color, const float* density, con
     const int groups = (int)min64(num_rays, min64(workspace_floats, (int64_t)1 << 22));
     const float inv_n = 1.0f / (float)(num_rays * 3);
     static const int waves = [] { const char* e = getenv("WISP_COMPOSITE_WAVES"); const int w = e ? atoi(e) : 4; return (w == 1 || w == 2) ? w : 4; }();
-    if (waves == 1)
+    // WISP_COMPOSITE_SPLIT (read on every call: a test flips it between two calls): 0 = composite_loss_kernel for every ray
+    const char* se = getenv("WISP_COMPOSITE_SPLIT");
+    const bool split = waves == 4 && groups == num_rays && !(se && atoi(se) == 0);
+    if (split)
+        hipLaunchKernelGGL(composite_loss_split_kernel<4>, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, color, density, deltas,
+                           ray_offsets, num_rays, b, gt, kind, inv_n, grad_color, grad_density, out_rgb, workspace);
+    else if (waves == 1)
         hipLaunchKernelGGL(composite_loss_kernel<1>, dim3(groups), dim3(64), 0, (hipStream_t)stream, color, density, deltas, ray_offsets,
                            num_rays, groups, b, gt, kind, inv_n, grad_color, grad_density, out_rgb, workspace);
     else if (waves == 2)

@@ -10,7 +10,8 @@
 // What it buys (measured, profiles/r06_native_step_ab.txt): the interpreter needs ~0.2 ms to issue a step through ctypes (13 calls, 19
 // allocations, ~70 pointer extractions; scripts/prof_step_host.py).  At the reference trainer's 2^18 packed samples per step the kernels
 // take ~0.30 ms and the step 0.34-0.38 ms: the host waits for the look-ahead read-back most of the time, i.e. it is NOT the bottleneck
-// there - the gaps of the kernel trace are the device's own launch-to-launch latency (16 dependent launches) - and the native step
+// there - the gaps of the kernel trace sit at the timing events below (NS_MARK: ~6 us per hipEventRecord between two launches, 0.0 us
+// at every boundary without one; profiles/step_timeline_2p18_long_rays_*.txt), not at the launches themselves - and the native step
 // is neutral (0.377 vs 0.377 ms in alternating bench runs, 1.10 vs 1.10 ms at 2^21).  Below ~2^17 samples per step the interpreter
 // becomes the longer of the two and the native step wins: 0.266 -> 0.251 ms at 2^16, 0.254 -> 0.232 ms at 2^15 (what one GPU of a
 // strong-scaled 8-GPU run at the reference's global batch would see).  It also takes the interpreter's jitter (collector pauses, a
