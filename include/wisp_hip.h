@@ -40,7 +40,8 @@ const char* wisp_last_error(void);
  * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
  * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
  * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused, wisp_raymarch_ray_emit_coded, wisp_nerf_mlp_operand_image_bytes,
- * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img - do not bump it). */
+ * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step - do not
+ * bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -561,6 +562,28 @@ int wisp_hash_sdf_trace_step_fused(int64_t num_packs, int first, const float* nu
                                    int codebook_bitwidth, int multiscale, int zero_from_col, const float* w1, const float* b1,
                                    const float* w2, const float* b2, int hidden, float scale, int32_t* any_active,
                                    wisp_stream_t stream);
+
+/* One optimisation step's forward + loss + backward of the reference's SDFTrainer (wisp/trainers/sdf_trainer.py:65-124 with
+ * only_last: loss = sum((pred - gt)^2) / n) for that field (csrc/hash_sdf_train.hip): what autograd runs over
+ * HashGrid.interpolate (wisp/models/grids/hash_grid.py:205-233; backward kernels hashgrid_interpolate_cuda.cu:214-339) and the decoder
+ * (wisp/models/nefs/neural_sdf.py:120-155), in two launches.  The hash-grid twin of wisp_sdf_train_step.
+ *  coords f32 [n,3], gts f32 [n], n >= 1; the hash field as above with feats_dtype f32 (the only table dtype under training);
+ *  grad_codebook f32 of the table's shape, grad_w1 / grad_b1 / grad_w2 / grad_b2 of their parameters' shapes: all five are ADDED
+ *  to; loss f32 [1] is written.  The predicted distance is bit for bit wisp_hash_sdf_query's.  Columns at or above zero_from_col
+ *  are neither gathered nor given a gradient ('cat' at lod_idx: the levels from lod_idx on stay untouched).
+ *  scratch: wisp_hash_sdf_train_scratch_bytes(...) bytes, contents irrelevant; that function returns -1 for a shape the step does
+ *  not serve (the limits above, or a decoder that does not fit one workgroup's LDS), and the step then returns WISP_ERR_INVALID
+ *  before any launch, as for every other failed check.
+ * The loss and the decoder's four gradients have a fixed summation order: bitwise repeatable.  The table gradient is summed with
+ * f32 atomic adds, like the reference's backward (levels of at most 2^16 entries: fp64 atomic adds into scratch, rounded once):
+ * repeatable only where its sums are exact. */
+int64_t wisp_hash_sdf_train_scratch_bytes(int64_t n, int num_lods, int feature_dim, int multiscale, int hidden);
+int wisp_hash_sdf_train_step(const float* coords, const float* gts, int64_t n, const void* codebook, int feats_dtype,
+                             const int64_t* begin_idxes, const int32_t* resolutions, int num_lods, int feature_dim,
+                             int codebook_bitwidth, int multiscale, int zero_from_col, const float* w1, const float* b1,
+                             const float* w2, const float* b2, int hidden, float* grad_codebook, float* grad_w1, float* grad_b1,
+                             float* grad_w2, float* grad_b2, float* loss, void* scratch, int64_t scratch_bytes,
+                             wisp_stream_t stream);
 
 /* Compositing + photometric loss + compositing backward of a TRAINING step in one launch (what
  * wisp/tracers/packed_rf_tracer.py:143-165, wisp/trainers/multiview_trainer.py:140-154 and their autograd backward do in

@@ -151,37 +151,6 @@ static_assert(((size_t)HSDF_MAX_HIDDEN * ((3 + HSDF_MAX_COLS) | 1) + 2 * HSDF_MA
               "the largest shape (hidden 256, 32 columns, 'sum' of 16 levels x 8) must fit the default dynamic LDS limit");
 static_assert(HSDF_MAX_LODS <= HG_MAX_LODS, "HashLevels holds the levels");
 
-static int hash_sdf_fill(HashSdfField& fld, const char* fn, const void* codebook, int dtype, const int64_t* begin_idxes,
-                         const int32_t* resolutions, int num_lods, int feature_dim, int codebook_bitwidth, int multiscale,
-                         int zero_from_col, const float* w1, const float* b1, const float* w2, const float* b2, int hidden) {
-#define HSDF_REQUIRE(cond, what) do { if (!(cond)) return wisp_fail(WISP_ERR_INVALID, fn, what); } while (0)
-    HSDF_REQUIRE(num_lods >= 1 && num_lods <= HSDF_MAX_LODS, "num_lods out of range (1..16)");
-    HSDF_REQUIRE(feature_dim == 2 || feature_dim == 4 || feature_dim == 8, "feature_dim must be 2, 4 or 8");
-    HSDF_REQUIRE(multiscale == 0 || multiscale == 1, "multiscale must be 0 ('cat') or 1 ('sum')");
-    const int cols = multiscale ? feature_dim : num_lods * feature_dim;
-    HSDF_REQUIRE(cols <= HSDF_MAX_COLS, "more than 32 feature columns");
-    HSDF_REQUIRE(hidden >= 1 && hidden <= HSDF_MAX_HIDDEN, "hidden width out of range");
-    HSDF_REQUIRE(codebook_bitwidth >= 1 && codebook_bitwidth <= 30, "codebook_bitwidth out of range");
-    HSDF_REQUIRE(zero_from_col >= 0, "zero_from_col is negative");
-    HSDF_REQUIRE(dtype == WISP_F32 || dtype == WISP_F16 || dtype == WISP_BF16, "bad dtype");
-    HSDF_REQUIRE(codebook && begin_idxes && resolutions && w1 && b1 && w2 && b2, "null pointer");
-    const int64_t tsize = (int64_t)1 << codebook_bitwidth;
-    HSDF_REQUIRE(fill_levels(resolutions, num_lods, 3, tsize, fld.lv) == 0, "bad resolution");
-    // every row a kernel can read lies inside the table: a hashed index is below 2^bitwidth, a dense one is pinned to the last row
-    HSDF_REQUIRE(begin_idxes[0] >= 0, "bad begin_idxes");
-    for (int l = 0; l < num_lods; ++l) {
-        const int64_t rows = begin_idxes[l + 1] - begin_idxes[l];
-        HSDF_REQUIRE(rows >= 1 && (fld.lv.dense[l] || rows >= tsize), "a level has fewer rows than its indices reach");
-    }
-#undef HSDF_REQUIRE
-    for (int l = 0; l <= HSDF_MAX_LODS; ++l) fld.begin[l] = begin_idxes[l <= num_lods ? l : num_lods];
-    fld.codebook = codebook; fld.tsize = (uint32_t)tsize;
-    fld.num_lods = num_lods; fld.feature_dim = feature_dim; fld.sum = multiscale; fld.zero_from_col = zero_from_col;
-    fld.cols = cols; fld.hidden = hidden;
-    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
-    return WISP_OK;
-}
-
 static inline size_t hash_sdf_lds(const HashSdfField& fld) {
     return hash_sdf_lds_bytes(fld.hidden, fld.cols, fld.num_lods, fld.feature_dim, fld.sum, HSDF_GROUPS);
 }

@@ -14,6 +14,9 @@
 // position; 'sum' adds the (rounded) levels in level order in fp32 and rounds through the table dtype once, as
 // Tensor.sum(-2) does on a half tensor.  The decoder is that of sdf_eval_point: hidden layer split over the lanes (weights in
 // LDS), fp32 fma chain in input order, the output dot product reduced with four shuffles of width 16.
+//
+// The end of the file is HOST code: hash_sdf_fill, the shape and pointer checks that fill a HashSdfField.  It lives here, next to the
+// struct it fills, because every entry point over such a field (hash_sdf_eval.hip, hash_sdf_train.hip) runs the same checks.
 #pragma once
 #include "wisp_common.h"
 #include "hashgrid_dev.h"
@@ -76,14 +79,16 @@ template <> __device__ __forceinline__ void hash_sdf_load_pair<__hip_bfloat16>(c
     a = __uint_as_float(v << 16); b = __uint_as_float(v & 0xffff0000u);
 }
 
-// All 16 lanes of a group call this together, with the same position.  c = lane within the group, gin = the group's floats of
-// LDS.  A group either runs the whole function or none of it (the shuffles stay inside the group).  Returns the raw decoder
-// output with the bias added.  Every rounding is spelled out - explicit fmaf, the compiler's own contraction switched off -
-// for the reason recorded at sdf_eval_coeffs (sdf_eval_dev.h): inlined copies of one function were scheduled differently and
-// returned different bits behind the rounding through a half table dtype.
+// The two halves of hash_sdf_eval_point below, separate so that the training step (hash_sdf_train.hip) runs the same statements
+// and keeps what its backward needs.  All 16 lanes of a group call them together, with the same position.  c = lane within the
+// group, gin = the group's floats of LDS.  Every rounding is spelled out - explicit fmaf, the compiler's own contraction switched
+// off - for the reason recorded at sdf_eval_coeffs (sdf_eval_dev.h): inlined copies of one function were scheduled differently
+// and returned different bits behind the rounding through a half table dtype.
+//
+// hash_sdf_point_inputs: the decoder inputs [position, features] of one position into gin[0 .. 3 + cols) (and, for 'sum', the level
+// blends behind them).  Ends with the wave barrier that makes them visible to the group.
 template <typename T>
-static __device__ __forceinline__ float hash_sdf_eval_point(const HashSdfField& fld, const HashSdfLds& s, float* gin, int c,
-                                                            float px, float py, float pz) {
+static __device__ __forceinline__ void hash_sdf_point_inputs(const HashSdfField& fld, float* gin, int c, float px, float py, float pz) {
 #pragma clang fp contract(off)
     const float pos[3] = {px, py, pz};
     const int F = fld.feature_dim;
@@ -132,7 +137,15 @@ static __device__ __forceinline__ float hash_sdf_eval_point(const HashSdfField& 
         }
         __builtin_amdgcn_wave_barrier();
     }
-    // ---- decoder: in = [position, features]
+}
+
+// hash_sdf_decode: the decoder over gin, in = [position, features]; returns the raw output with the bias added.  KEEP (the training
+// step): lane c also leaves, for its hidden units hh = c, c + 16, ..., w2[hh] where the unit is active (0 elsewhere) in ga[hh] and
+// the unit's relu output in gr[hh] - stores only, the arithmetic is the same statements.
+template <bool KEEP>
+static __device__ __forceinline__ float hash_sdf_decode(const HashSdfField& fld, const HashSdfLds& s, const float* gin, int c,
+                                                        float* ga, float* gr) {
+#pragma clang fp contract(off)
     const int in_dim = 3 + fld.cols;
     float o = 0.0f;
     for (int hh = c; hh < fld.hidden; hh += HSDF_GROUP) {
@@ -140,8 +153,54 @@ static __device__ __forceinline__ float hash_sdf_eval_point(const HashSdfField& 
         float a = s.b1[hh];
         for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
         o = __builtin_fmaf(s.w2[hh], fmaxf(a, 0.0f), o);
+        if (KEEP) {
+            ga[hh] = a > 0.0f ? s.w2[hh] : 0.0f;
+            gr[hh] = fmaxf(a, 0.0f);
+        }
     }
 #pragma unroll
     for (int d = HSDF_GROUP / 2; d >= 1; d >>= 1) o += __shfl_xor(o, d, HSDF_GROUP);
     return o + fld.b2[0];
+}
+
+// A group either runs the whole function or none of it (the shuffles stay inside the group).
+template <typename T>
+static __device__ __forceinline__ float hash_sdf_eval_point(const HashSdfField& fld, const HashSdfLds& s, float* gin, int c,
+                                                            float px, float py, float pz) {
+    hash_sdf_point_inputs<T>(fld, gin, c, px, py, pz);
+    return hash_sdf_decode<false>(fld, s, gin, c, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+// The shape and pointer checks of a hash field, shared by every entry point over it (hash_sdf_eval.hip, hash_sdf_train.hip):
+// nothing is dereferenced but the two HOST arrays, and nothing is launched.
+static inline int hash_sdf_fill(HashSdfField& fld, const char* fn, const void* codebook, int dtype, const int64_t* begin_idxes,
+                         const int32_t* resolutions, int num_lods, int feature_dim, int codebook_bitwidth, int multiscale,
+                         int zero_from_col, const float* w1, const float* b1, const float* w2, const float* b2, int hidden) {
+#define HSDF_REQUIRE(cond, what) do { if (!(cond)) return wisp_fail(WISP_ERR_INVALID, fn, what); } while (0)
+    HSDF_REQUIRE(num_lods >= 1 && num_lods <= HSDF_MAX_LODS, "num_lods out of range (1..16)");
+    HSDF_REQUIRE(feature_dim == 2 || feature_dim == 4 || feature_dim == 8, "feature_dim must be 2, 4 or 8");
+    HSDF_REQUIRE(multiscale == 0 || multiscale == 1, "multiscale must be 0 ('cat') or 1 ('sum')");
+    const int cols = multiscale ? feature_dim : num_lods * feature_dim;
+    HSDF_REQUIRE(cols <= HSDF_MAX_COLS, "more than 32 feature columns");
+    HSDF_REQUIRE(hidden >= 1 && hidden <= HSDF_MAX_HIDDEN, "hidden width out of range");
+    HSDF_REQUIRE(codebook_bitwidth >= 1 && codebook_bitwidth <= 30, "codebook_bitwidth out of range");
+    HSDF_REQUIRE(zero_from_col >= 0, "zero_from_col is negative");
+    HSDF_REQUIRE(dtype == WISP_F32 || dtype == WISP_F16 || dtype == WISP_BF16, "bad dtype");
+    HSDF_REQUIRE(codebook && begin_idxes && resolutions && w1 && b1 && w2 && b2, "null pointer");
+    const int64_t tsize = (int64_t)1 << codebook_bitwidth;
+    HSDF_REQUIRE(fill_levels(resolutions, num_lods, 3, tsize, fld.lv) == 0, "bad resolution");
+    // every row a kernel can read lies inside the table: a hashed index is below 2^bitwidth, a dense one is pinned to the last row
+    HSDF_REQUIRE(begin_idxes[0] >= 0, "bad begin_idxes");
+    for (int l = 0; l < num_lods; ++l) {
+        const int64_t rows = begin_idxes[l + 1] - begin_idxes[l];
+        HSDF_REQUIRE(rows >= 1 && (fld.lv.dense[l] || rows >= tsize), "a level has fewer rows than its indices reach");
+    }
+#undef HSDF_REQUIRE
+    for (int l = 0; l <= HSDF_MAX_LODS; ++l) fld.begin[l] = begin_idxes[l <= num_lods ? l : num_lods];
+    fld.codebook = codebook; fld.tsize = (uint32_t)tsize;
+    fld.num_lods = num_lods; fld.feature_dim = feature_dim; fld.sum = multiscale; fld.zero_from_col = zero_from_col;
+    fld.cols = cols; fld.hidden = hidden;
+    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
+    return WISP_OK;
 }

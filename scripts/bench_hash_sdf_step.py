@@ -1,0 +1,105 @@
+"""ms per optimisation step of the hash-grid SDF application (NeuralSDF over a HashGrid, nglod_hash.yaml: 'cat', 4 levels x 8
+features, resolutions 16 .. 2048, tables of 2^19 rows, hidden 128) on the procedural torus of scripts/train_sdf_tex.py, four ways, at
+512 coordinates per step (the config's batch) and at 2^16: one JSON line.
+
+  * train_step_eager_modular     SDFTrainStep.step as a trainer built without fused_hash runs it: autograd over the modular launches
+                                 + the single-launch optimizer - the only way to fit this field before the fused step;
+  * train_step_eager_fused       SDFTrainStep(fused_hash=True).step: wisp_hash_sdf_train_step (two launches) + the optimizer;
+  * train_step_captured_fused    the same, forward + loss + backward replayed as a HIP graph;
+  * train_step_captured_modular  the graph of the modular launches.
+Every figure is the median of `--reps` (at least 5) repetitions of `--steps` steps each between two HIP events, the four variants
+taking turns inside one process; every variant trains its own copy of the same initial field on the same batches.
+
+    python scripts/bench_hash_sdf_step.py [--reps 7] [--steps 200] [--out profiles/bench_hash_sdf_step.json]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import tempfile
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd"), os.path.join(ROOT, "scripts")]
+
+from bench_sdf_tex_step import _alternate                                # noqa: E402
+
+
+def measure(nef, coords, sdf, B, reps, inner):
+    """the four variants at batch size B -> (median ms, min ms, final losses)"""
+    from wisp.trainers import SDFTrainStep
+    n_batches = max(coords.shape[0] // B, 1)
+    batches = [(coords[i * B:(i + 1) * B].contiguous(), sdf[i * B:(i + 1) * B].reshape(-1, 1).contiguous()) for i in range(n_batches)]
+    assert batches[0][0].shape[0] == B, "the dataset is smaller than one batch"
+    turn = {}
+
+    def nxt(name):
+        turn[name] = (turn.get(name, -1) + 1) % n_batches
+        return batches[turn[name]]
+
+    nefs = [copy.deepcopy(nef) for _ in range(4)]
+    eager_modular = SDFTrainStep(nefs[0], lr=1e-3, eps=1e-15)
+    assert eager_modular._fused_field() is None
+    eager = SDFTrainStep(nefs[1], lr=1e-3, eps=1e-15, fused_hash=True)
+    assert eager._fused_field() is not None
+    graph_fused = SDFTrainStep(nefs[2], lr=1e-3, eps=1e-15, fused_hash=True).capture(B)
+    assert graph_fused._fused_field() is not None
+    graph_modular = SDFTrainStep(nefs[3], lr=1e-3, eps=1e-15).capture(B)
+    assert graph_modular._fused_field() is None
+    cases = {"train_step_eager_modular": lambda: eager_modular.step(*nxt("m")),
+             "train_step_eager_fused": lambda: eager.step(*nxt("e")),
+             "train_step_captured_fused": lambda: graph_fused.step(*nxt("gf")),
+             "train_step_captured_modular": lambda: graph_modular.step(*nxt("gm"))}
+    med, low = _alternate(cases, reps, inner)
+    final = {k: float(v) for k, v in (("eager_modular", eager_modular.step(*batches[0])), ("eager_fused", eager.step(*batches[0])),
+                                      ("captured_fused", graph_fused.step(*batches[0])),
+                                      ("captured_modular", graph_modular.step(*batches[0])))}
+    return med, low, final
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--steps", type=int, default=200, help="steps between the two events of one repetition (a quarter of it at 2^16)")
+    ap.add_argument("--level", type=int, default=6)
+    ap.add_argument("--codebook-bitwidth", type=int, default=19)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_hash_sdf_step.py measures on the GPU"
+    import train_nglod
+    import train_sdf_tex
+    dev = "cuda:0"
+    reps = max(args.reps, 5)
+    torch.manual_seed(0)
+    with tempfile.TemporaryDirectory() as tmp:
+        obj = train_sdf_tex.write_test_mesh(tmp)
+        ds, pipe = train_nglod.build(obj, dev, level=args.level, num_samples=1 << 18, num_samples_on_mesh=500_000, grid_type="hash",
+                                     codebook_bitwidth=args.codebook_bitwidth)
+    nef = pipe.nef
+    coords, sdf = ds.data["coords"].to(dev), ds.data["sdf"].to(dev)
+    result = dict(metric="hash_sdf_step",
+                  source=f"HIP events around {args.steps} steps ({max(args.steps // 4, 1)} at 2^16), median of {reps} alternating "
+                         f"repetitions in one process",
+                  device=torch.cuda.get_device_name(0), level=args.level, num_lods=nef.grid.num_lods, feature_dim=nef.grid.feature_dim,
+                  codebook_bitwidth=args.codebook_bitwidth, hidden=nef.decoder.layers[0].out_features, samples=int(coords.shape[0]))
+    for B, inner in ((512, args.steps), (1 << 16, max(args.steps // 4, 1))):
+        med, low, final = measure(nef, coords, sdf, B, reps, inner)
+        result[f"batch_{B}"] = dict(**{k + "_ms": round(v, 4) for k, v in med.items()},
+                                    **{"min_" + k + "_ms": round(v, 4) for k, v in low.items()},
+                                    eager_modular_over_eager_fused=round(med["train_step_eager_modular"] / med["train_step_eager_fused"], 2),
+                                    eager_modular_over_captured_fused=round(med["train_step_eager_modular"] / med["train_step_captured_fused"], 2),
+                                    captured_modular_over_captured_fused=round(med["train_step_captured_modular"] /
+                                                                               med["train_step_captured_fused"], 2),
+                                    final_losses=final)
+    text = json.dumps(result)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

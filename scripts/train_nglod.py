@@ -10,8 +10,9 @@ snapshot (render.png) and the three axis-aligned distance cross-sections (slice_
 as a HIP graph for whole batches) instead of SDFTrainer's torch.optim loop; validation is SDFTrainer.validate either way.
 --grid hash fits the field of nglod_hash.yaml instead: HashGrid.from_geometric, 'cat', 4 levels x 8 features between resolutions
 16 and 2048, tables of 2^19 rows (--codebook-bitwidth for smaller ones).  Validation, the snapshot and the slices then run through
-the kernels of csrc/hash_sdf_eval.hip; SDFTrainStep has no fused step for a hash grid, so --fused-step trains through its modular
-launches there (and without the graph).
+the kernels of csrc/hash_sdf_eval.hip, and --fused-step trains through wisp_hash_sdf_train_step (csrc/hash_sdf_train.hip:
+SDFTrainStep(..., fused_hash=True)), replayed as a HIP graph like the octree step; the JSON record's fused_hash_step says whether
+the field took that branch.
 The last line printed is one JSON record with the IoU before and after training."""
 import argparse
 import json
@@ -55,10 +56,12 @@ def fit_fused(trainer, ds, cfg, device):
     from wisp.trainers import SDFTrainStep
     oc, bs = cfg.optimizer, cfg.dataloader.batch_size
     nef = trainer.pipeline.nef
+    from wisp.models.grids import HashGrid, OctreeGrid
     step = SDFTrainStep(nef, lr=oc.lr, eps=oc.eps, grid_lr_weight=cfg.grid_lr_weight, betas=oc.betas, optimizer='adam',
-                        only_last=cfg.only_last)
-    from wisp.models.grids import OctreeGrid
-    if torch.device(device).type == 'cuda' and len(ds) >= bs and type(nef.grid) is OctreeGrid:
+                        only_last=cfg.only_last, fused_hash=type(nef.grid) is HashGrid)
+    on_gpu = torch.device(device).type == 'cuda'
+    fused_hash_step = bool(on_gpu and step.fused_hash and step._fused_field() is not None)
+    if on_gpu and len(ds) >= bs and (type(nef.grid) is OctreeGrid or fused_hash_step):
         step.capture(bs)
     nef.train()
     for epoch in range(cfg.max_epochs):
@@ -73,6 +76,7 @@ def fit_fused(trainer, ds, cfg, device):
             ds.resample()
             trainer.init_dataloader()
     nef.eval()
+    return fused_hash_step
 
 
 def main(argv=None):
@@ -118,8 +122,9 @@ def main(argv=None):
     before = trainer.validate()
     metric = next(iter(before))
     t0 = time.time()
+    fused_hash_step = False
     if args.fused_step:
-        fit_fused(trainer, ds, cfg, args.device)
+        fused_hash_step = fit_fused(trainer, ds, cfg, args.device)
     else:
         trainer.train()
     if torch.cuda.is_available():
@@ -140,6 +145,7 @@ def main(argv=None):
         vis = renderer.sdf_slice(pipeline.nef, dim=axis)
         save_u8(files[f"slice_{name}"], (np.clip(vis, 0, 1) * 255).round().astype(np.uint8).transpose(1, 0, 2))
     rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, grid=args.grid, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
+               fused_hash_step=fused_hash_step,
                metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
                seconds=round(seconds, 3), **{k: os.path.abspath(v) for k, v in files.items()})
     print(json.dumps(rec))
