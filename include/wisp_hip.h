@@ -40,8 +40,8 @@ const char* wisp_last_error(void);
  * wisp_sdf_train_step, wisp_hashgrid_grad_coords, wisp_host_reader_*, wisp_nerf_step_*, wisp_mesh_to_sdf*, wisp_multiview_sample,
  * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
  * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused, wisp_raymarch_ray_emit_coded, wisp_nerf_mlp_operand_image_bytes,
- * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step - do not
- * bump it). */
+ * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step,
+ * wisp_image_field_train_step - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -994,6 +994,36 @@ int wisp_image_field_render(const float* coords, int64_t first, int64_t n, int h
                             int codebook_bitwidth, const float* weights, int hidden_padded, const uint8_t* gts, float* out_f32,
                             uint8_t* out_u8, double* err_partials, wisp_stream_t stream);
 int64_t wisp_image_field_render_partials(int64_t n);
+
+/* One optimisation step's forward + loss + backward of the reference's ImageTrainer (wisp/trainers/image_trainer.py:52-84, `step`:
+ * loss = F.mse_loss(nef.rgb(coords), rgb), backward) for the field above (wisp/models/nefs/image_nef.py:66-97 over
+ * HashGrid.interpolate, wisp/models/grids/hash_grid.py:205-233; backward kernels hashgrid_interpolate_cuda.cu:214-339), in two
+ * launches and one memset (csrc/image_field_train.hip).  The image twin of wisp_hash_sdf_train_step.
+ *  coords f32 [n,2], rgb f32 [n,3], 1 <= n <= 2^22 (so that (float)(3 n) is exact);
+ *  codebook f32 [rows,2], resolutions i32 [num_lods] (HOST), num_lods <= 16, active_lods and codebook_bitwidth as for
+ *  wisp_image_field_render; first_idx i64 [num_lods + 1] is a HOST array here - the step checks every level's rows against the
+ *  indices the kernels can form before it launches anything;
+ *  w1 f32 [hidden][2 num_lods + 14], b1 [hidden], w2 [3][hidden], b2 [3]: torch's native layout, 1 <= hidden <= 128; the library
+ *  stages them itself (no packing on the caller's side);
+ *  grad_codebook f32 of the table's shape, grad_w1 / grad_b1 / grad_w2 / grad_b2 of their parameters' shapes: all five are ADDED
+ *  to; loss f32 [1] is written; pred f32 [n,3] or NULL: the predicted colours.
+ * Forward: steps 2 - 6 of wisp_image_field_render through the same __device__ functions (csrc/image_field_dev.h): pred is bit for
+ * bit that entry point's out_f32 for coords.  The columns of the levels from active_lods on contribute nothing: their rows and
+ * their W1 columns receive no gradient (rows stay bitwise untouched, the W1 columns have zero added).
+ * Loss: d = s - t in fp32, loss = (float)(S / (double)(3 n)) with S the fp64 sum of the fp32 squares d * d in a fixed order;
+ * g = 2 d / (float)(3 n) (IEEE division), d output = g * (s * (1 - s)).  Sums over outputs, hidden units and samples run in fp64
+ * and are rounded to fp32 once.  The embedding columns get a W1 gradient; nothing consumes d / d coordinate.
+ *  scratch: wisp_image_field_train_scratch_bytes(...) bytes, 8-byte aligned, contents irrelevant; that function returns -1 for a
+ *  shape the step does not serve, and the step then returns WISP_ERR_INVALID before any launch, as for every other failed check.
+ * The loss and the decoder's four gradients have a fixed summation order: bitwise repeatable.  The table gradient is summed with
+ * fp64 atomic adds into scratch on levels of at most 2^16 entries (rounded once) and with f32 atomic adds on larger ones, like the
+ * reference's backward: repeatable to the last bits of those sums, bitwise where they are exact. */
+int64_t wisp_image_field_train_scratch_bytes(int64_t n, int num_lods, int hidden);
+int wisp_image_field_train_step(const float* coords, const float* rgb, int64_t n, const float* codebook, const int64_t* first_idx,
+                                const int32_t* resolutions, int num_lods, int active_lods, int codebook_bitwidth, const float* w1,
+                                const float* b1, const float* w2, const float* b2, int hidden, float* grad_codebook,
+                                float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, float* loss, float* pred,
+                                void* scratch, int64_t scratch_bytes, wisp_stream_t stream);
 
 #ifdef __cplusplus
 }

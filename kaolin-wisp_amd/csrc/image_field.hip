@@ -14,17 +14,14 @@
 // Level arithmetic: corner_setup of hashgrid_dev.h, the library's own.  The gather and the blend of the four corners RESTATE
 // the plain path of hashgrid_fwd_kernel (hashgrid.hip: `acc[k] += table[idx[j]][k] * coef[j]`, corners in index order, the
 // res >= 258 clamp of dense levels included) without its packed-load special cases, which change no bit.
+// The per-pixel forward - level blend, embedding, decoder, sigmoid - lives in image_field_dev.h as __device__ functions, which the
+// fused training step (image_field_train.hip) calls as well: a colour is the same bits in both.
 // Numerics contract: include/wisp_hip.h (wisp_image_field_render), DESIGN.md section 7.
 #include "wisp_common.h"
 #include "hashgrid_dev.h"
+#include "image_field_dev.h"
 
 #define IF_THREADS 256
-#define IF_MAX_LODS 16
-#define IF_EMBED 14                               // x, y, sin / cos of (x, y) * (1, 2, 4)
-#define IF_IN (IF_MAX_LODS * 2 + IF_EMBED)        // rows of the packed first layer: 32 feature rows (absent levels: zero), 14 embedding
-#define IF_PIECE 32                               // hidden units per pass
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // torch.linspace(start, end, steps)[i] in fp32 (aten RangeFactories: two-sided, one fused multiply-add per element)
 static __device__ __forceinline__ float linspace_at(float start, float end, float step, int steps, int i) {
@@ -112,73 +109,18 @@ image_field_render_kernel(const float* __restrict__ coords, int64_t first, int64
     for (int l = 0; l < IF_MAX_LODS; ++l) {
         float acc[2] = {0.0f, 0.0f};
         if (l < active_lods && live) {
-            const int32_t res = lv.res[l];
-            const bool dense = lv.dense[l] != 0;
-            const float* __restrict__ table = codebook + first_idx[l] * 2;
             CornerSetup<2> cs;
-            corner_setup<2>(c, res, lv.hi[l], lv.hr[l], dense, tsize, tsize_pow2 != 0, cs);
-            if (dense && res >= 258) {                                     // as hashgrid_fwd_kernel: the read is pinned to the table's last row
-                const int64_t last = first_idx[num_lods] - 1 - first_idx[l];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if ((int64_t)(uint32_t)cs.idx[j] > last) cs.idx[j] = (int32_t)last;
-            }
-            float2 v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float2*>(table + (int64_t)cs.idx[j] * 2);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { acc[0] += v[j].x * cs.coef[j]; acc[1] += v[j].y * cs.coef[j]; }
+            image_level_corners(c, lv.res[l], lv.hi[l], lv.hr[l], lv.dense[l] != 0, tsize, tsize_pow2 != 0, first_idx[l],
+                                first_idx[num_lods], cs);
+            image_level_blend(codebook + first_idx[l] * 2, cs, acc);
         }
         x[2 * l] = acc[0]; x[2 * l + 1] = acc[1];
     }
-    // ---- positional embedding, PositionalEmbedder's layout: [x, y | sin(1x) sin(1y) sin(2x) sin(2y) sin(4x) sin(4y) | cos(same)]
-    {
-        float* e = x + 2 * IF_MAX_LODS;
-        e[0] = c[0]; e[1] = c[1];
-#pragma unroll
-        for (int f = 0; f < 3; ++f)
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const float t = c[a] * (float)(1 << f);                    // exact: a power of two
-                e[2 + f * 2 + a] = sinf(t);
-                e[8 + f * 2 + a] = cosf(t);
-            }
-    }
-    // ---- decoder: 32 hidden units at a time; every weight is a scalar operand
-    const float* __restrict__ b1 = weights + (size_t)IF_IN * hp;
-    const float* __restrict__ w2 = b1 + hp;
-    const float* __restrict__ b2 = w2 + 3 * (size_t)hp;
-    float o0 = b2[0], o1 = b2[1], o2 = b2[2];
-    for (int piece = 0; piece < hp; piece += IF_PIECE) {
-        float hacc[IF_PIECE];
-        {
-            const f32x16 ba = *reinterpret_cast<const f32x16*>(b1 + piece), bb = *reinterpret_cast<const f32x16*>(b1 + piece + 16);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) { hacc[j] = ba[j]; hacc[16 + j] = bb[j]; }
-        }
-#pragma unroll
-        for (int k = 0; k < IF_IN; ++k) {
-            const float* __restrict__ wr = weights + (size_t)k * hp + piece;
-            const f32x16 wa = *reinterpret_cast<const f32x16*>(wr), wb = *reinterpret_cast<const f32x16*>(wr + 16);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                hacc[j] = __builtin_fmaf(x[k], wa[j], hacc[j]);
-                hacc[16 + j] = __builtin_fmaf(x[k], wb[j], hacc[16 + j]);
-            }
-        }
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const f32x16 u0 = *reinterpret_cast<const f32x16*>(w2 + piece + half * 16);
-            const f32x16 u1 = *reinterpret_cast<const f32x16*>(w2 + hp + piece + half * 16);
-            const f32x16 u2 = *reinterpret_cast<const f32x16*>(w2 + 2 * hp + piece + half * 16);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float a = fmaxf(hacc[half * 16 + j], 0.0f);
-                o0 = __builtin_fmaf(a, u0[j], o0); o1 = __builtin_fmaf(a, u1[j], o1); o2 = __builtin_fmaf(a, u2[j], o2);
-            }
-        }
-    }
-    float col[3] = {1.0f / (1.0f + expf(-o0)), 1.0f / (1.0f + expf(-o1)), 1.0f / (1.0f + expf(-o2))};
+    // ---- positional embedding, then the decoder and the sigmoid (image_field_dev.h)
+    image_embed(c, x + 2 * IF_MAX_LODS);
+    float o[3];
+    image_decode_packed(x, weights, hp, o);
+    float col[3] = {image_sigmoid(o[0]), image_sigmoid(o[1]), image_sigmoid(o[2])};
     double err = 0.0;
     if (live) {
         if (out_f32) { out_f32[i * 3] = col[0]; out_f32[i * 3 + 1] = col[1]; out_f32[i * 3 + 2] = col[2]; }

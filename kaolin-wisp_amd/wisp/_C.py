@@ -152,10 +152,13 @@ SIGNATURES = {
     "wisp_image_field_render": [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp,
                                 c_vp, c_vp],
     "wisp_image_field_render_partials": [c_i64],
+    "wisp_image_field_train_scratch_bytes": [c_i64, c_i32, c_i32],
+    "wisp_image_field_train_step": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
-_RESTYPES = {"wisp_image_field_render_partials": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
+_RESTYPES = {"wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
              "wisp_last_error": ctypes.c_char_p, "wisp_host_reader_create": c_vp, "wisp_host_reader_destroy": None,
              "wisp_nerf_step_config_bytes": c_i64, "wisp_nerf_step_workspace_bytes": c_i64, "wisp_nerf_step_create": c_vp,
              "wisp_nerf_step_destroy": None}
@@ -1776,6 +1779,44 @@ def image_field_render(h, w, first, n, codebook, first_idx, resolutions, codeboo
                                        int(active_lods), int(codebook_bitwidth), _p(packed), int(hp), _p(gts_u8) if want_err else None,
                                        _p(out_f32), _p(out_u8), _p(part), _stream()), "image_field_render")
     return out_f32, out_u8, part
+
+
+_image_train_scratch = _Scratch(zeroed=False)   # (ImageTrainStep.capture bakes its address into a HIP graph)
+
+
+def image_field_train_step(coords, rgb, fld, grad_table, grad_w1, grad_b1, grad_w2, grad_b2, want_pred=False):
+    """Forward + loss + backward of one image-fitting step (wisp_image_field_train_step, csrc/image_field_train.hip): coords
+    [n, 2], rgb [n, 3] -> (loss f32 [1] = F.mse_loss(pred, rgb), pred f32 [n, 3] or None).  fld: dict of codebook (f32 [rows, 2]),
+    begin_idxes and resolutions (HOST lists), codebook_bitwidth, active_lods (the number of levels rgb() blends) and the decoder
+    in torch's native layout: w1 [H, 2 L + 14], b1 [H], w2 [3, H], b2 [3].  The gradients are ADDED to grad_table (the table's
+    shape) and grad_w1 / b1 / w2 / b2.  The scratch is cached per (device, stream): a captured graph finds it allocated."""
+    coords = _need(coords, torch.float32, "coords")
+    rgb = _need(rgb, torch.float32, "rgb")
+    cb, w1, b1, w2, b2 = fld["codebook"], fld["w1"], fld["b1"], fld["w2"], fld["b2"]
+    res = [int(r) for r in fld["resolutions"]]
+    begin = [int(b) for b in fld["begin_idxes"]]
+    n, dev, L, H = coords.shape[0], coords.device, len(res), w1.shape[0]
+    if tuple(coords.shape) != (n, 2) or tuple(rgb.shape) != (n, 3) or rgb.device != dev:
+        raise RuntimeError(f"image_field_train_step: coords must be [n, 2] and rgb [n, 3], got {tuple(coords.shape)} / {tuple(rgb.shape)}")
+    assert cb.is_cuda and cb.is_contiguous() and cb.dtype == torch.float32 and cb.dim() == 2 and cb.shape[1] == 2
+    assert len(begin) == L + 1 and begin[-1] == cb.shape[0]
+    assert tuple(w1.shape) == (H, 2 * L + 14) and b1.numel() == H and tuple(w2.shape) == (3, H) and b2.numel() == 3
+    for g, q in ((grad_table, cb), (grad_w1, w1), (grad_b1, b1), (grad_w2, w2), (grad_b2, b2)):
+        assert g.device == dev and q.device == dev and q.dtype == torch.float32 and q.is_contiguous()
+        assert g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == tuple(q.shape)
+    need = int(lib.wisp_image_field_train_scratch_bytes(n, L, H))
+    if need < 0:
+        raise RuntimeError(f"image_field_train_step: unsupported shape (n {n}, lods {L}, hidden {H})")
+    scratch = _image_train_scratch.get(dev, need)
+    bi = (ctypes.c_int64 * (L + 1))(*begin)
+    rs = (ctypes.c_int32 * L)(*res)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    pred = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_pred else None
+    _check(lib.wisp_image_field_train_step(_p(coords), _p(rgb), n, _p(cb), bi, rs, L, int(fld["active_lods"]),
+                                           int(fld["codebook_bitwidth"]), _p(w1), _p(b1), _p(w2), _p(b2), H, _p(grad_table), _p(grad_w1),
+                                           _p(grad_b1), _p(grad_w2), _p(grad_b2), _p(loss), _p(pred), _p(scratch), scratch.numel(),
+                                           _stream()), "image_field_train_step")
+    return loss, pred
 
 
 def mesh_to_sdf(points, mesh, with_triangle=False, triangle_ranges=0, max_pairs_per_launch=0):

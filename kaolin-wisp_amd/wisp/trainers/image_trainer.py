@@ -124,10 +124,15 @@ class ImageTrainStep:
     """SDFTrainStep's pattern for the image field: parameters re-homed into one flat buffer (FlatParams), forward and backward
     through the modular 2-D lookup and decoder under autograd in fp32, loss = F.mse_loss, one fused optimizer launch that also
     zeroes the gradients.  `lr` is a plain attribute read at every step, so a MultiStepLR-style schedule is driven from outside
-    (`set_schedule` installs image_hash.yaml's).  capture(batch_size) records forward + loss + backward as one HIP graph."""
+    (`set_schedule` installs image_hash.yaml's).  capture(batch_size) records forward + loss + backward as one HIP graph.
+    fused=True takes forward + loss + backward through wisp_image_field_train_step (csrc/image_field_train.hip: two launches)
+    whenever the field is that kernel's shape (_fused_field), and the modular launches otherwise; the default leaves every launch
+    where it was."""
 
-    def __init__(self, nef, lr=1e-3, eps=1e-16, weight_decay=0.0, grid_lr_weight=1.0, betas=(0.9, 0.999), optimizer='adam'):
+    def __init__(self, nef, lr=1e-3, eps=1e-16, weight_decay=0.0, grid_lr_weight=1.0, betas=(0.9, 0.999), optimizer='adam',
+                 fused=False):
         self.nef = nef
+        self.fused = bool(fused)
         self.flat = FlatParams(nef)
         self.lr, self.eps, self.weight_decay, self.grid_lr_weight, self.betas = lr, eps, weight_decay, grid_lr_weight, betas
         self.optimizer = str(optimizer).lower()
@@ -161,7 +166,65 @@ class ImageTrainStep:
                             self.opt_steps, zero_grad=True)
         self.lr = self.scheduled_lr()
 
+    def _fused_field(self):
+        """What wisp_image_field_train_step needs, or None: only in a step built with fused=True, for the field shape of
+        fused_render_shape (a 'cat' HashGrid without a BLAS, two f32 features per entry, at most 16 levels, the 3-octave embedder,
+        one hidden relu Linear layer of at most 128 units with biases, 3 outputs), with f32, contiguous parameters and gradients
+        on the GPU.  WISP_IMAGE_TRAIN_FUSED=0 keeps the modular launches (so does WISP_IMAGE_RENDER_FUSED=0, which makes
+        fused_render_shape decline), and so does a batch of more than 2^22 pixels.  The shape checks are cached; what can change under a
+        live trainer is looked at on every call (_fused_still_valid)."""
+        if not self.fused:
+            return None
+        cached = getattr(self, "_fused_cache", None)
+        if cached is not None:
+            if cached and not self._fused_still_valid(cached):
+                cached = self._fused_cache = None                  # re-derive below
+            else:
+                return cached or None
+        self._fused_cache = False
+        if os.environ.get("WISP_IMAGE_TRAIN_FUSED", "1") == "0":
+            return None
+        from wisp.models.nefs.image_nef import fused_render_shape
+        shape = fused_render_shape(self.nef)
+        if shape is None:
+            return None
+        grid, l1, lout = shape
+        if not (1 <= l1.out_features <= 128 and lout.in_features == l1.out_features):
+            return None
+        prm = [grid.codebook.feats, l1.weight, l1.bias, lout.weight, lout.bias]
+        if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.grad is not None and q.grad.is_contiguous()
+                   and q.grad.dtype == torch.float32 and q.grad.is_cuda for q in prm):
+            return None
+        # the host-side description is kept (begin_idxes comes from a device tensor); the tensors are taken anew at every step.
+        # rgb()'s default lod = num_lods - 1 blends the levels below it: the finest level is inert ('cat', hash_grid.py:226-229)
+        host = dict(begin_idxes=grid.codebook.begin_idxes.tolist(), resolutions=grid.codebook.resolutions.reshape(-1).tolist(),
+                    codebook_bitwidth=int(grid.codebook_bitwidth), active_lods=grid.num_lods - 1)
+        self._fused_cache = dict(grid=grid, dec=self.nef.decoder, l1=l1, lout=lout, lods=grid.num_lods, prm=prm, host=host)
+        return self._fused_cache
+
+    def _fused_still_valid(self, c):
+        nef = self.nef
+        grid, dec = c["grid"], c["dec"]
+        if not self.fused or getattr(nef, "grid", None) is not grid or getattr(nef, "decoder", None) is not dec \
+                or grid.num_lods != c["lods"] or dec.layers[0] is not c["l1"] or dec.lout is not c["lout"]:
+            return False
+        now = [grid.codebook.feats, c["l1"].weight, c["l1"].bias, c["lout"].weight, c["lout"].bias]
+        for q, was in zip(now, c["prm"]):
+            g = q.grad
+            if q is not was or g is None or g.dtype != torch.float32 or not g.is_contiguous() or not q.is_contiguous() \
+                    or q.dtype != torch.float32:
+                return False
+        return True
+
     def _forward_backward(self, coords, rgb):
+        fused = None
+        if self.fused and coords.is_cuda and rgb.is_cuda and coords.ndim == 2 and rgb.ndim == 2 and 0 < coords.shape[0] <= (1 << 22) \
+                and coords.shape[1] == 2 and tuple(rgb.shape) == (coords.shape[0], 3) and coords.dtype == rgb.dtype == torch.float32:
+            fused = self._fused_field()
+        if fused is not None:
+            table, (w1, b1, w2, b2) = fused["prm"][0], fused["prm"][1:]
+            fld = dict(fused["host"], codebook=table.detach(), w1=w1.detach(), b1=b1.detach(), w2=w2.detach(), b2=b2.detach())
+            return _hip().image_field_train_step(coords, rgb, fld, table.grad, w1.grad, b1.grad, w2.grad, b2.grad)[0][0]
         loss = F.mse_loss(self.nef.rgb(coords), rgb)
         loss.backward()
         return loss.detach()

@@ -5,7 +5,9 @@
     2^18 indices of a 4096^2 image;
   * whole-image validation render (u8 image + squared error against the bank) at 4096^2 and 16384^2 on the same trained field:
     the fused launch of csrc/image_field.hip against 1 M-pixel chunks of nef.rgb - the path that exists without it;
-  * ms per step at 4 096 pixels: ImageTrainer (torch.optim, fp16 autocast) against ImageTrainStep eager and captured.
+  * ms per step at 4 096 pixels: ImageTrainer (torch.optim, fp16 autocast) against ImageTrainStep eager and captured, modular
+    (autograd over the ops) and fused (ImageTrainStep(fused=True): wisp_image_field_train_step, csrc/image_field_train.hip) -
+    five rows, with the spread (max - min over the repetitions) of every row.
 Every figure is the median of `--reps` (at least 5) repetitions, the alternatives alternating inside one process; times are HIP
 events around the launches (`inner` launches per repetition for the microsecond cases).  The fused render's fraction of the fp32
 vector peak counts 2 x (46 x hidden + 3 x hidden) flops per pixel against 157.3 TFLOP/s.
@@ -37,15 +39,17 @@ def _time(fn, inner=1):
     return a.elapsed_time(b) / inner                                   # ms
 
 
-def _alternate(cases, reps, inner=1):
-    """cases: {name: fn}.  One warm-up each, then `reps` rounds in which the cases take turns.  -> {name: median ms}"""
+def _alternate(cases, reps, inner=1, with_max=False):
+    """cases: {name: fn}.  One warm-up each, then `reps` rounds in which the cases take turns.  -> ({name: median ms}, {name: min ms})
+    and, with_max, {name: max ms} as a third member"""
     for fn in cases.values():
         fn()
     times = {k: [] for k in cases}
     for _ in range(reps):
         for k, fn in cases.items():
             times[k].append(_time(fn, inner))
-    return {k: statistics.median(v) for k, v in times.items()}, {k: min(v) for k, v in times.items()}
+    out = {k: statistics.median(v) for k, v in times.items()}, {k: min(v) for k, v in times.items()}
+    return out + ({k: max(v) for k, v in times.items()},) if with_max else out
 
 
 def _bank(side, dev):
@@ -138,20 +142,29 @@ def bench_step(reps, dev, steps=100):
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "bench.png")
         save_u8(path, train_image.procedural_image(1024, 1024))
-        made = [build(path, dev) for _ in range(3)]
+        made = [build(path, dev) for _ in range(5)]
     ds = made[0][0]
+    for _, pipeline in made[1:]:                                       # (ImageTrainer moves its own pipeline)
+        pipeline.nef.to(dev)
     trainer = ImageTrainer(trainer_config(100), made[0][1], ds, device=dev)
     trainer.pre_training()
     eager = ImageTrainStep(made[1][1].nef, lr=1e-3, eps=1e-16, weight_decay=1e-6, grid_lr_weight=500.0)
     graph = ImageTrainStep(made[2][1].nef, lr=1e-3, eps=1e-16, weight_decay=1e-6, grid_lr_weight=500.0).capture(4096)
 
+    fused = ImageTrainStep(made[3][1].nef, lr=1e-3, eps=1e-16, weight_decay=1e-6, grid_lr_weight=500.0, fused=True)
+    fused_graph = ImageTrainStep(made[4][1].nef, lr=1e-3, eps=1e-16, weight_decay=1e-6, grid_lr_weight=500.0, fused=True).capture(4096)
+    assert fused._fused_field() is not None and fused_graph._fused_field() is not None
+
     def dropin():
         c, p = ds[0]
         trainer.step([c[None], p[None]])
-    med, low = _alternate({"image_trainer": dropin, "train_step_eager": lambda: eager.step(*ds[0]),
-                           "train_step_captured": lambda: graph.step(*ds[0])}, reps, inner=steps)
+    cases = {"image_trainer": dropin, "train_step_eager": lambda: eager.step(*ds[0]),
+             "train_step_captured": lambda: graph.step(*ds[0]), "train_step_fused": lambda: fused.step(*ds[0]),
+             "train_step_fused_captured": lambda: fused_graph.step(*ds[0])}
+    med, low, high = _alternate(cases, reps, inner=steps, with_max=True)
     return dict(pixels_per_step=4096, steps_per_rep=steps, **{k + "_ms": round(v, 4) for k, v in med.items()},
-                **{"min_" + k + "_ms": round(v, 4) for k, v in low.items()})
+                **{"min_" + k + "_ms": round(v, 4) for k, v in low.items()},
+                **{"spread_" + k + "_ms": round(high[k] - low[k], 4) for k in med})
 
 
 def main():

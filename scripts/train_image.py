@@ -3,13 +3,16 @@ ImageDataset (u8 bank on the GPU, fused sampling), HashGrid.from_geometric(blas=
 Adam (lr 1e-3, eps 1e-16, weight decay 1e-6), grid lr x 500 and the MultiStepLR schedule, validation (whole-image render, PSNR,
 img_pred.png / img_gts.png) at the end.
 
-    python scripts/train_image.py IMAGE [--epochs N] [--fused-step] [--log-dir DIR]
+    python scripts/train_image.py IMAGE [--epochs N] [--fused-step] [--fused-kernel] [--log-dir DIR]
     python scripts/train_image.py --write-test-image PATH [--size H W] ...
 
 --write-test-image PATH first writes a procedural RGB PNG to PATH and then fits it, so the script runs where no image exists.
 --fused-step trains with ImageTrainStep (flat parameter buffer, single-launch optimizer, forward + backward replayed as a HIP
 graph) instead of ImageTrainer's torch.optim loop; validation is ImageTrainer's in both cases.
-The last line printed is one JSON record: PSNR after the first epoch and after training, seconds, ms per step."""
+--fused-kernel (implies --fused-step) builds ImageTrainStep(..., fused=True): forward + loss + backward run through
+wisp_image_field_train_step (csrc/image_field_train.hip, two launches) instead of the modular ops under autograd.
+The last line printed is one JSON record: PSNR after the first epoch and after training, seconds, ms per step, and
+fused_image_step - whether the steps went through that kernel."""
 import argparse
 import json
 import logging
@@ -66,6 +69,7 @@ def main(argv=None):
     ap.add_argument("--hidden-dim", type=int, default=64)
     ap.add_argument("--codebook-bitwidth", type=int, default=19)
     ap.add_argument("--fused-step", action="store_true")
+    ap.add_argument("--fused-kernel", action="store_true", help="ImageTrainStep(fused=True): the two-launch training kernel; implies --fused-step")
     ap.add_argument("--no-amp", action="store_true")
     ap.add_argument("--log-dir", default=os.path.join("_results", "logs", "runs", "image-hash"))
     ap.add_argument("--device", default="cuda")
@@ -89,10 +93,12 @@ def main(argv=None):
     steps_per_epoch = trainer.iterations_per_epoch
     total = steps_per_epoch * args.epochs
     t0 = time.time()
-    if args.fused_step:
+    fused_image_step = False
+    if args.fused_step or args.fused_kernel:
         oc = trainer.cfg.optimizer
         step = ImageTrainStep(pipeline.nef, lr=oc.lr, eps=oc.eps, weight_decay=oc.weight_decay, grid_lr_weight=trainer.cfg.grid_lr_weight,
-                              betas=oc.betas, optimizer='adam')
+                              betas=oc.betas, optimizer='adam', fused=args.fused_kernel)
+        fused_image_step = bool(args.fused_kernel and step._fused_field() is not None)
         step.set_schedule([total * x for x in trainer.cfg.scheduler_milestones], trainer.cfg.scheduler_gamma)
         step.capture(args.num_pixels)
         first = None
@@ -120,7 +126,8 @@ def main(argv=None):
         torch.cuda.synchronize()
     seconds = time.time() - t0
     final = trainer.validate()['psnr']
-    print(json.dumps(dict(image=os.path.abspath(path), h=ds.h, w=ds.w, step="ImageTrainStep" if args.fused_step else "ImageTrainer",
+    print(json.dumps(dict(image=os.path.abspath(path), h=ds.h, w=ds.w, step="ImageTrainStep" if args.fused_step or args.fused_kernel else "ImageTrainer",
+                          fused_image_step=fused_image_step,
                           epochs=args.epochs, steps=total, psnr_first_epoch=first, psnr=final, seconds=round(seconds, 3),
                           ms_per_step=round(1e3 * seconds / total, 4), log_dir=os.path.abspath(args.log_dir))))
     return final
