@@ -236,7 +236,8 @@ def test_composite_loss_in_one_launch_equals_the_three_launches(kind):
     for _ in range(3):
         again = C.composite_loss(c, d, dl, o, R, bg, g, kind)
         assert float(again[0]) == float(loss1) and torch.equal(again[1], gc1) and torch.equal(again[2], gd1) and again[3] is None
-    # more rays than workgroups (grid-stride over rays) and a single ray
+    # 20 000 short rays and a single ray.  (No grid-stride walk over rays here: wisp._C.composite_loss hands the library a partial-sum
+    #  cell per ray, so every ray has a wave of its own; tests/test_gpu_composite_exact.py reaches the walk through the C entry point.)
     big = np.concatenate([[0], np.cumsum(rng.integers(0, 6, 20000))]).astype(np.int64)
     Sb = int(big[-1])
     cb, db, dlb = cuda(rng.uniform(0, 1, (Sb, 3)).astype(np.float32)), cuda(rng.uniform(0, 20, (Sb, 1)).astype(np.float32)), cuda(np.full((Sb, 1), 0.01, np.float32))
