@@ -41,7 +41,7 @@ const char* wisp_last_error(void);
  * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
  * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused, wisp_raymarch_ray_emit_coded, wisp_nerf_mlp_operand_image_bytes,
  * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step,
- * wisp_image_field_train_step - do not bump it). */
+ * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug - do not bump it). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -648,6 +648,33 @@ int wisp_nerf_mlp_bwd(const void* feats, int dtype_io, const float* dirs, int64_
                       void* grad_feats /* dtype_io [S,in_dim] */, float* grad_params /* accumulated */,
                       float* workspace, int64_t workspace_bytes /* >= wisp_nerf_mlp_bwd_workspace_bytes() */,
                       wisp_stream_t stream);
+
+/* The density query of the occupancy prune (NeuralRadianceField.prune, wisp/models/nefs/nerf.py:175-212) as ONE launch: for every
+ * cell i of the dense level `level` (res = 2^level) the sample position ((dense_points[i] + unit_samples[i]) / res) * 2 - 1, the
+ * lookup of the levels below zero_from_col on the fp32 table, layers 1 and 2 of the exact-fp32 decoder, and
+ *   occ_out[i] = max(relu(y0), occ_in[i] * decay)        keep[i] = occ_out[i] > min_density
+ * Bit for bit what the position arithmetic of torch, wisp_hashgrid_interpolate_fwd and wisp_nerf_mlp_fwd (WISP_F32 compute) give
+ * for the same inputs; no feature tensor exists, the view direction and layers 3-5 (which the density does not depend on) are
+ * not evaluated.
+ *  dense_points  i16 [cells, 3]     unit_samples  f32 [cells, 3] in [0, 1)
+ *  table, first_idx, resolutions, codebook_bitwidth, zero_from_col (a multiple of feature_dim): as wisp_hashgrid_interpolate_fwd
+ *  params        f32 packed as for wisp_nerf_mlp_fwd (only W1, b1, W2, b2 are read)
+ *  occ_in, occ_out f32 [cells] (may not alias), keep u8 [cells]
+ * This build: feature_dim 2, coord_dim 3, num_lods <= 16, hidden 64, in_dim = num_lods * 2 (<= 32), dtype_table = dtype_params =
+ * WISP_F32; anything else returns WISP_ERR_UNSUPPORTED before any launch.
+ * wisp_nerf_prune_query_debug (tests): the same launch also writes the decoder's input rows (feats f32 [cells, in_dim]) and the
+ * density (f32 [cells]), so that a mismatch can be pinned on the lookup or on the decoder. */
+int wisp_nerf_prune_query(const int16_t* dense_points, const float* unit_samples, int64_t cells, int level, const void* table,
+                          int dtype_table, int feature_dim, int coord_dim, const int64_t* first_idx, const int32_t* resolutions,
+                          int num_lods, int codebook_bitwidth, int zero_from_col, const float* params, int dtype_params, int in_dim,
+                          int hidden, const float* occ_in, float decay, float min_density, float* occ_out, uint8_t* keep,
+                          wisp_stream_t stream);
+int wisp_nerf_prune_query_debug(const int16_t* dense_points, const float* unit_samples, int64_t cells, int level, const void* table,
+                                int dtype_table, int feature_dim, int coord_dim, const int64_t* first_idx,
+                                const int32_t* resolutions, int num_lods, int codebook_bitwidth, int zero_from_col,
+                                const float* params, int dtype_params, int in_dim, int hidden, const float* occ_in, float decay,
+                                float min_density, float* occ_out, uint8_t* keep, float* feats, float* density,
+                                wisp_stream_t stream);
 
 /* The same decoder with the view direction given per RAY.  The reference gathers a direction per sample
  * (wisp/tracers/packed_rf_tracer.py:70-76 `rays.dirs.index_select(0, ridx)`) and positional_embedder.py:61-65 encodes each

@@ -110,6 +110,35 @@ static __device__ __forceinline__ void corner_setup(const float* __restrict__ c,
 #undef HG_CORNER_TERMS
 }
 
+// One level of the lookup on an fp32 table of two features per row (the master table of nerf_hash.yaml), for kernels that fuse the
+// lookup with what consumes it (prune_query.hip) - in three steps, so that a caller can have the gathers of several levels in
+// flight before it blends the first.
+// Dense level with res >= 258: the fp32 clamp bound rounds up to res - 1, so a corner can be `res` and its index can
+// leave the level; the reference then reads the next level's rows, and past the allocation on the last level, which is the one
+// case refused: the read is pinned to the table's last row (`last` = rows from the level's first row to the table's last one).
+template <int DIM>
+static __device__ __forceinline__ void corner_pin(CornerSetup<DIM>& cs, int64_t last) {
+#pragma unroll
+    for (int j = 0; j < (1 << DIM); ++j)
+        if ((int64_t)(uint32_t)cs.idx[j] > last) cs.idx[j] = (int32_t)last;
+}
+template <int DIM>
+static __device__ __forceinline__ void corner_gather_f32x2(const float* __restrict__ table, const CornerSetup<DIM>& cs,
+                                                           float2 (&v)[1 << DIM]) {
+#pragma unroll
+    for (int j = 0; j < (1 << DIM); ++j) v[j] = *reinterpret_cast<const float2*>(table + (int64_t)(uint32_t)cs.idx[j] * 2);
+}
+// the blend, in hashgrid_fwd_kernel's order: acc = fmaf(v_j, coef_j, acc), j = 0 .. 2^DIM - 1, from 0
+template <int DIM>
+static __device__ __forceinline__ void corner_blend_f32x2(const float2 (&v)[1 << DIM], const CornerSetup<DIM>& cs, float& a0, float& a1) {
+    a0 = 0.0f; a1 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < (1 << DIM); ++j) {
+        a0 = __builtin_fmaf(v[j].x, cs.coef[j], a0);
+        a1 = __builtin_fmaf(v[j].y, cs.coef[j], a1);
+    }
+}
+
 // Per-level constants, computed once on the host.
 static inline int fill_levels(const int32_t* resolutions, int num_lods, int coord_dim, int64_t tsize, HashLevels& lv) {
     for (int l = 0; l < num_lods; ++l) {

@@ -22,9 +22,8 @@
 // Fixed shape of this build: IN = 32 grid features, H = 64 hidden, 4 view frequencies (nerf_hash.yaml).
 #include "wisp_common.h"
 #include "nerf_mlp_shape.h"
+#include "nerf_mlp_f32_dev.h"
 #include <cstdlib>
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -67,10 +66,7 @@ template <typename TC> struct MMA;
 template <> struct MMA<float> {
     template <int K>
     static __device__ __forceinline__ void nt(const float* A, int lda, const float* B, int ldb, floatx16& acc, int lane) {
-        const float* pa = A + (lane & 31) * lda + (lane >> 5);
-        const float* pb = B + (lane & 31) * ldb + (lane >> 5);
-#pragma unroll
-        for (int k = 0; k < K; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[k], pb[k], acc, 0, 0, 0);
+        f32_mma_nt<K>(A, lda, B, ldb, acc, lane);             // nerf_mlp_f32_dev.h
     }
     // D[k][n] += sum_i W[i][krow0 + k] * dY[n][i]     (reduction over M rows of W)
     template <int M>
@@ -106,15 +102,7 @@ static __device__ __forceinline__ void dw_layer(const float* dY, int ldy, const 
     }
 }
 
-// row of accumulator register `reg` for this lane (C/D layout of the 32x32 MFMA shapes)
-static __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
-static __device__ __forceinline__ floatx16 zero16() {
-    floatx16 z;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = 0.0f;
-    return z;
-}
+// (acc_row, zero16: nerf_mlp_f32_dev.h)
 
 template <typename T> static __device__ __forceinline__ float io_to_f(T v);
 template <> __device__ __forceinline__ float io_to_f<float>(float v) { return v; }
@@ -220,31 +208,14 @@ nerf_mlp_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, i
         }
         __builtin_amdgcn_wave_barrier();
 
-        // ---- L1: h1 = relu(W1 x0 + b1)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            floatx16 acc = zero16();
-            MMA<TC>::template nt<IN>(sw + G::W1 + t * 32 * G::LDI, G::LDI, x0, G::LDI, acc, lane);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = t * 32 + acc_row(r, lane);
-                h1[n * G::LDH + row] = Tr::from_f(fmaxf(acc[r] + sb[G::B1 + row], 0.0f));
-            }
-        }
+        // ---- L1: h1 = relu(W1 x0 + b1), L2: y = W2 h1 + b2 ; density = relu(y0) ; geometry features y[1..15] -> x2[:, 0..14]
+        // (nerf_mlp_f32_dev.h: the fused prune query runs the same two stages)
+        static_assert(G::LDI == F32_LDI && G::LDH == F32_LDH && sizeof(TC) == sizeof(float), "the shared stages are the fp32 layout");
+        WISP_F32_LAYER1(sw, G::W1, sb, G::B1, x0, h1, n, lane)
         __builtin_amdgcn_wave_barrier();
-        // ---- L2: y = W2 h1 + b2 ; density = relu(y0) ; geometry features y[1..15] -> x2[:, 0..14]
         float y0 = 0.0f;
-        {
-            floatx16 acc = zero16();
-            MMA<TC>::template nt<H>(sw + G::W2, G::LDH, h1, G::LDH, acc, lane);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {                       // rows 0..15 live in regs 0..7 (rows 16.. are padding)
-                const int row = acc_row(r, lane);
-                const float y = acc[r] + sb[G::B2 + row];
-                if (row == 0) y0 = y; else x2[n * G::LDH + row - 1] = Tr::from_f(y);
-            }
-            if (half == 0 && live && !BWD) out_density[s] = fmaxf(y0, 0.0f);
-        }
+        WISP_F32_LAYER2(sw, G::W2, sb, G::B2, h1, n, lane, y0, true, x2)
+        if (half == 0 && live && !BWD) out_density[s] = fmaxf(y0, 0.0f);
         __builtin_amdgcn_wave_barrier();
         // ---- L3: h2 = relu(W3 x2 + b3)
 #pragma unroll

@@ -119,6 +119,10 @@ SIGNATURES = {
     "wisp_nerf_mlp_param_count": [c_i32, c_i32, c_i32],
     "wisp_nerf_mlp_fwd": [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_bwd": [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "wisp_nerf_prune_query": [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
+                              c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp],
+    "wisp_nerf_prune_query_debug": [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                    c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_dir_code": [c_vp, c_i64, c_i32, c_vp, c_vp],
     "wisp_nerf_mlp_operand_image_bytes": [c_i32],
     "wisp_nerf_mlp_build_operand_image": [c_vp, c_i32, c_i32, c_vp, c_vp],
@@ -1990,6 +1994,54 @@ def nerf_mlp_forward(feats, dirs, params, in_dim, hidden, view_freqs, compute_bf
         _check(lib.wisp_nerf_mlp_fwd(_p(feats), _DTYPE_CODE[feats.dtype], _p(dirs), S, in_dim, hidden, view_freqs, _p(params),
                                      BF16 if compute_bf16 else F32, _p(rgb), _p(density), _stream()), "nerf_mlp_fwd")
     return rgb, density
+
+
+def nerf_prune_query(dense_points, unit_samples, level, codebook, first_idx, resolutions, codebook_bitwidth, zero_from_col, params,
+                     in_dim, hidden, occupancy, decay, min_density, debug=False, pad_rows=0):
+    """(occ_out f32 [cells], keep bool [cells]) - the density query of NeuralRadianceField.prune in one launch
+    (wisp_nerf_prune_query): occ_out = max(density, occupancy * decay), keep = occ_out > min_density, bit for bit what the modular
+    path (position arithmetic, hashgrid_interpolate on the fp32 table, nerf_mlp_forward with fp32 compute, maximum, >) returns.
+    debug=True -> (occ_out, keep, feats [cells, in_dim], density [cells]) from wisp_nerf_prune_query_debug.
+    pad_rows (tests): the outputs are allocated with that many extra rows behind the last cell, filled with a sentinel (NaN / 255)
+    that the launch must leave alone, and returned WITH them."""
+    dense_points = _need(dense_points, torch.int16, "dense_points")
+    unit_samples = _need(unit_samples, torch.float32, "unit_samples")
+    codebook = _need(codebook, None, "codebook")
+    first_idx = _need(first_idx, torch.int64, "codebook_first_idx")
+    params = _need(params, None, "params")
+    occupancy = _need(occupancy, torch.float32, "occupancy")
+    cells = dense_points.shape[0]
+    if dense_points.shape != (cells, 3) or unit_samples.shape != (cells, 3) or occupancy.shape != (cells,):
+        raise ValueError(f"dense_points / unit_samples must be [cells, 3] and occupancy [cells]; got {tuple(dense_points.shape)}, "
+                         f"{tuple(unit_samples.shape)}, {tuple(occupancy.shape)}")
+    L, F = len(resolutions), codebook.shape[1]
+    first_host = _check_first_idx(first_idx, L, codebook.shape[0])
+    # every live level must own the rows its indices can reach (MultiTable's own rule: min(2^bitwidth, res^3) rows per level)
+    for l in range(min(L, -(-zero_from_col // max(F, 1)))):
+        need = min(1 << codebook_bitwidth, int(resolutions[l]) ** 3)
+        if first_host[l + 1] - first_host[l] < need:
+            raise RuntimeError(f"nerf_prune_query: level {l} (res {resolutions[l]}) owns {first_host[l + 1] - first_host[l]} rows, "
+                               f"its indices reach {need}")
+    want = int(lib.wisp_nerf_mlp_param_count(in_dim, hidden, 4))
+    if params.numel() != want:
+        raise ValueError(f"packed decoder parameters: expected {want} floats for in_dim={in_dim}, got {params.numel()}")
+    _, res_arr, res_ptr = _host_res(resolutions)
+    dev = dense_points.device
+    occ_out = torch.empty(cells + pad_rows, dtype=torch.float32, device=dev)
+    keep = torch.empty(cells + pad_rows, dtype=torch.uint8, device=dev)
+    if pad_rows:
+        occ_out[cells:] = float("nan")
+        keep[cells:] = 255
+    head = (_p(dense_points), _p(unit_samples), cells, int(level), _p(codebook), _DTYPE_CODE.get(codebook.dtype, -1), F,
+            dense_points.shape[1], _p(first_idx), res_ptr, L, codebook_bitwidth, zero_from_col, _p(params),
+            _DTYPE_CODE.get(params.dtype, -1), in_dim, hidden, _p(occupancy), float(decay), float(min_density), _p(occ_out), _p(keep))
+    if not debug:
+        _check(lib.wisp_nerf_prune_query(*head, _stream()), "nerf_prune_query")
+        return occ_out if pad_rows else occ_out[:cells], (keep if pad_rows else keep[:cells].view(torch.bool))
+    feats = torch.empty(cells, in_dim, dtype=torch.float32, device=dev)
+    density = torch.empty(cells, dtype=torch.float32, device=dev)
+    _check(lib.wisp_nerf_prune_query_debug(*head, _p(feats), _p(density), _stream()), "nerf_prune_query_debug")
+    return occ_out if pad_rows else occ_out[:cells], (keep if pad_rows else keep[:cells].view(torch.bool)), feats, density
 
 
 def nerf_mlp_dir_code(ray_dirs, view_freqs=4):

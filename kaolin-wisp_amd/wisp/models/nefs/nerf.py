@@ -100,6 +100,8 @@ class NeuralRadianceField(BaseNeuralField):
         if not isinstance(self.grid, HashGrid):
             raise NotImplementedError(f'Pruning not implemented for grid type {self.grid.__class__.__name__}')
         device = self.device
+        if self.prune_fused():
+            return self._prune_fused(device, unit_samples, view_dirs)
         self.grid.occupancy = self.grid.occupancy.to(device) * self.prune_density_decay
         if self.grid.dense_points.device != device:
             self.grid.dense_points = self.grid.dense_points.to(device)       # once: 12 MB at level 7, not per prune
@@ -137,6 +139,34 @@ class NeuralRadianceField(BaseNeuralField):
         if kept.shape[0] == 0:
             return
         self.grid.blas = blas_cls.from_quantized_points(kept, level)
+
+    def prune_fused(self):
+        """True when prune() takes the one-launch density query (csrc/prune_query.hip) instead of interpolate + decoder: see
+        wisp.ops.nerf_mlp.prune_query_supported.  The results are the same bits either way; WISP_PRUNE_FUSED=0 forces the modular
+        path.  (A caller that prepares `view_dirs` may skip its arithmetic when this holds: no output depends on them.)"""
+        if self.prune_density_decay is None or self.prune_min_density is None or self.grid is None:
+            return False
+        from wisp.ops.nerf_mlp import prune_query_supported
+        return prune_query_supported(self)
+
+    def _prune_fused(self, device, unit_samples, view_dirs):
+        from wisp.ops.nerf_mlp import fused_prune_query
+        grid = self.grid
+        grid.occupancy = grid.occupancy.to(device)
+        if grid.dense_points.device != device:
+            grid.dense_points = grid.dense_points.to(device)
+        cells = grid.dense_points.shape[0]
+        # every draw of the modular path, in its order, so that whatever reads the generators next sees the same stream; the
+        # sphere arithmetic on the second one is skipped - the density does not depend on the view direction
+        if unit_samples is None:
+            unit_samples = torch.rand(cells, 3, device=device)
+        if view_dirs is None:
+            torch.rand(2, cells, device=device)
+        with torch.no_grad():
+            grid.occupancy, keep = fused_prune_query(self, unit_samples.to(device))
+        new_blas = grid.blas.__class__.from_leaf_mask(keep, grid.blas.max_level)
+        if new_blas is not None:
+            grid.blas = new_blas
 
     # ------------------------------------------------------------------ forward
     def register_forward_functions(self):

@@ -107,6 +107,48 @@ def supports(nef, feats):
             and nef.layer_type in ('linear', 'none') and feats.dtype in (torch.float32, torch.float16, torch.bfloat16))
 
 
+def prune_query_supported(nef):
+    """The fused density query of the prune (csrc/prune_query.hip) covers this field: a CUDA 'cat' HashGrid of two-feature 3-D
+    levels (at most 16) with an fp32 master table, the fused decoder at hidden 64 with fp32 compute, and dense_points holding
+    every cell of the octree's finest level (what BLAS.from_leaf_mask needs).  WISP_PRUNE_FUSED=0 switches it off."""
+    import os
+    from wisp.models.grids import HashGrid
+    if os.environ.get("WISP_PRUNE_FUSED", "1") == "0" or not getattr(nef, 'fused_decoder', False) or torch.is_autocast_enabled():
+        return False
+    grid = nef.grid
+    if not isinstance(grid, HashGrid) or grid.multiscale_type != 'cat' or grid.coord_dim != 3 or grid.feature_dim != 2 \
+            or not 1 <= grid.num_lods <= 16 or len(grid.active_lods) != grid.num_lods or getattr(grid, 'blas', None) is None:
+        return False
+    table = grid.codebook.feats
+    if not table.is_cuda or table.dtype != torch.float32 or nef.hidden_dim != SUPPORTED["hidden"] or _compute_bf16(nef):
+        return False
+    from types import SimpleNamespace
+    if not supports(nef, SimpleNamespace(is_cuda=True, shape=(0, nef.effective_feature_dim()), dtype=torch.float32)):
+        return False                                       # (what the lookup would hand the decoder: fp32 rows on the table's device)
+    if any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in _decoder_tensors(nef)[:4]):
+        return False
+    level = grid.blas.max_level
+    return (hasattr(grid.blas.__class__, "from_leaf_mask") and grid.dense_points.shape[0] == 8 ** level and level <= 9)
+
+
+def fused_prune_query(nef, unit_samples, debug=False, pad_rows=0):
+    """(new occupancy f32 [cells], keep bool [cells]) of NeuralRadianceField.prune for a field prune_query_supported() accepts;
+    nef.grid.occupancy is the occupancy BEFORE the decay."""
+    C = _hip()
+    grid = nef.grid
+    cb = grid.codebook
+    params = _decoder_tensors(nef)
+    H, I = nef.hidden_dim, nef.effective_feature_dim()
+    shapes = ((H, I), (H,), (16, H), (16,), (H, 42), (H,), (H, H), (H,), (3, H), (3,))
+    flat = _flat_view([p.detach() if p is not None else None for p in params])
+    packed = flat if flat is not None else _pack(params, shapes)
+    lod_idx = len(grid.active_lods) - 1                   # what NeuralRadianceField.rgba queries; 'cat' zeroes the columns from there on
+    res = [int(r) for r in cb.resolutions.reshape(-1).tolist()]
+    return C.nerf_prune_query(grid.dense_points, unit_samples, grid.blas.max_level, cb.feats.detach(), cb.begin_idxes, res,
+                              grid.codebook_bitwidth, lod_idx * grid.feature_dim, packed, I, H, grid.occupancy,
+                              nef.prune_density_decay, nef.prune_min_density, debug=debug, pad_rows=pad_rows)
+
+
 def fused_nerf_decoder(nef, feats, ray_d):
     """(rgb [S,3] fp32, density [S,1] fp32) for the decoder shapes of the reference's app/nerf configs (see SUPPORTED)."""
     compute_bf16 = _compute_bf16(nef)

@@ -859,7 +859,9 @@ class MultiviewTrainStep:
         cells = nef.grid.dense_points.shape[0]
         dev = self._prune_gen.device
         unit = torch.rand(cells, 3, generator=self._prune_gen, device=dev)
-        views = torch.nn.functional.normalize(torch.randn(cells, 3, generator=self._prune_gen, device=dev), dim=1)
+        views = torch.randn(cells, 3, generator=self._prune_gen, device=dev)
+        if not (hasattr(nef, 'prune_fused') and nef.prune_fused()):
+            views = torch.nn.functional.normalize(views, dim=1)      # (the fused density query reads no view direction)
         nef.prune(unit_samples=unit, view_dirs=views)
 
     def calc_adaptive_rays(self, num_rays_in_batch):
