@@ -41,7 +41,10 @@ const char* wisp_last_error(void);
  * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
  * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused, wisp_raymarch_ray_emit_coded, wisp_nerf_mlp_operand_image_bytes,
  * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step,
- * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug - do not bump it). */
+ * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_composite_loss_partials, wisp_loss_sum,
+ * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
+ * wisp_hashgrid_interpolate_bwd_adamw_tail - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -130,6 +133,32 @@ int wisp_hashgrid_interpolate_bwd_adamw(const float* coords, int64_t n, int coor
                                         const float* level_cap_scale, float* param, float* exp_avg, float* exp_avg_sq,
                                         void* bf16_shadow, float lr, float beta1, float beta2, float eps, float weight_decay,
                                         int64_t step, float grad_scale, int64_t* covered_rows /* host */, wisp_stream_t stream);
+
+/* The two small sums that close a training step's backward, carried by the reduce launch of the call above instead of by launches of
+ * their own (bodies: csrc/step_tail_dev.h): dec_grad[packed(j)] += sum of the decoder's dW partial rows (what
+ * wisp_nerf_mlp_reduce_partials does) and loss[0] = inv_n * sum of the loss partials (wisp_loss_sum).  Same order of additions, same
+ * bits.  Either half is skipped when its pointers are NULL.  The partials must have been written by launches ahead of this call on
+ * the same stream; dec_grad and loss are complete when the call's last launch is. */
+typedef struct wisp_step_tail {
+    const float* dw_partials;        /* [dw_rows][wisp_nerf_mlp partial row] as wisp_nerf_mlp_bwd_rays*_partials leave them */
+    float* dec_grad;                 /* packed decoder gradient, accumulated into */
+    const float* loss_partials;      /* [loss_count] as wisp_composite_loss_partials leaves them */
+    float* loss;                     /* f32 [1] */
+    int32_t dw_rows, in_dim, loss_count;
+    float inv_n;
+} wisp_step_tail;
+/* *tail_done (host): 1 = the sums went with the reduce launch; 0 = that launch did not happen in the form that carries them (fewer
+ * than 4096 samples, a workspace too small to bin, not a two-feature table): the caller launches wisp_nerf_mlp_reduce_partials and
+ * wisp_loss_sum itself.  Everything else as wisp_hashgrid_interpolate_bwd_adamw. */
+int wisp_hashgrid_interpolate_bwd_adamw_tail(const float* coords, int64_t n, int coord_dim,
+                                             const void* grad_feats, int dtype, int feature_dim,
+                                             const int64_t* first_idx, const int32_t* resolutions, int num_lods,
+                                             int codebook_bitwidth, int zero_from_col,
+                                             float* grad_codebook, void* workspace, int64_t workspace_bytes,
+                                             const float* level_cap_scale, float* param, float* exp_avg, float* exp_avg_sq,
+                                             void* bf16_shadow, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                             int64_t step, float grad_scale, int64_t* covered_rows /* host */,
+                                             const wisp_step_tail* tail, int* tail_done /* host */, wisp_stream_t stream);
 
 /* Diagnostic (no counterpart in the reference's bindings): the integer cell, the position inside it and the 2^d corner rows
  * (relative to the level's first row) that ONE level assigns to every coordinate - the first lines of every reference
@@ -599,6 +628,15 @@ int wisp_composite_loss(const float* color, const float* density, const float* d
                         int64_t num_rays, int64_t num_samples, const float* bg, const float* gt, int kind,
                         float* grad_color, float* grad_density, float* out_rgb, float* loss, float* workspace,
                         int64_t workspace_floats, wisp_stream_t stream);
+/* wisp_composite_loss = wisp_composite_loss_partials + wisp_loss_sum.  The first is the compositing launch alone: it leaves
+ * *num_partials (host) loss partials at the start of `workspace` and *inv_n (host) = 1 / (3 num_rays); the second is the one-workgroup
+ * launch that adds num_partials partials in a fixed order and writes loss[0] = inv_n * sum.  (The native training step lets the
+ * hash-grid reduce launch do the second: wisp_step_tail.) */
+int wisp_composite_loss_partials(const float* color, const float* density, const float* deltas, const int64_t* ray_offsets,
+                                 int64_t num_rays, int64_t num_samples, const float* bg, const float* gt, int kind,
+                                 float* grad_color, float* grad_density, float* out_rgb, float* workspace,
+                                 int64_t workspace_floats, int* num_partials /* host */, float* inv_n /* host */, wisp_stream_t stream);
+int wisp_loss_sum(const float* partials, int num_partials, float inv_n, float* loss, wisp_stream_t stream);
 
 /* Photometric loss of MultiviewTrainer.step (wisp/trainers/multiview_trainer.py:140-154) and its gradient in one launch:
  * loss[0] = mean over the num_elements entries of huber(beta = 1) (kind 0) / squared (1) / absolute (2) error of rgb
@@ -710,6 +748,19 @@ int wisp_nerf_mlp_bwd_rays_img(const void* feats, int dtype_io, const void* dir_
                                int in_dim, int hidden, int view_freqs, const float* params, const void* image,
                                const float* grad_rgb, const float* grad_density, void* grad_feats, float* grad_params,
                                float* workspace, int64_t workspace_bytes, wisp_stream_t stream);
+/* wisp_nerf_mlp_bwd_rays / _bwd_rays_img = their _partials form + wisp_nerf_mlp_reduce_partials.  The _partials forms launch the
+ * chain kernel only: grad_feats is complete, the parameter gradient is left as *partial_rows (host) rows in `workspace`;
+ * wisp_nerf_mlp_reduce_partials adds those rows into grad_params (packed, W1 in_dim wide) in a fixed order.  (The native training
+ * step lets the hash-grid reduce launch do that: wisp_step_tail.) */
+int wisp_nerf_mlp_bwd_rays_partials(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx, int64_t num_samples,
+                                    int in_dim, int hidden, int view_freqs, const float* params, const float* grad_rgb,
+                                    const float* grad_density, void* grad_feats, float* workspace, int64_t workspace_bytes,
+                                    int* partial_rows /* host */, wisp_stream_t stream);
+int wisp_nerf_mlp_bwd_rays_img_partials(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx, int64_t num_samples,
+                                        int in_dim, int hidden, int view_freqs, const float* params, const void* image,
+                                        const float* grad_rgb, const float* grad_density, void* grad_feats, float* workspace,
+                                        int64_t workspace_bytes, int* partial_rows /* host */, wisp_stream_t stream);
+int wisp_nerf_mlp_reduce_partials(const float* workspace, int partial_rows, int in_dim, float* grad_params, wisp_stream_t stream);
 
 /* One-hidden-layer relu decoder with a single output, out = W2 relu(W1 x + b1) + b2 - the NeuralSDF decoder
  * (wisp/models/nefs/neural_sdf.py:102-118; nglod_octree.yaml: 19 -> 128 -> 1; BasicDecoder.forward,
@@ -832,7 +883,10 @@ typedef struct wisp_nerf_step_hyper {
     int32_t optimizer;               /* 0: none (gradients are left accumulated: the caller exchanges / applies them);
                                         1: one AdamW launch over all groups; 2: the table's AdamW folded into its backward
                                         (wisp_hashgrid_interpolate_bwd_adamw) + one launch for everything else */
-    int32_t reserved;
+    int32_t tail_fold;               /* with optimizer == 2: 1 = the decoder's dW sum and the loss sum ride in the hash-grid reduce
+                                        launch (wisp_step_tail) instead of being launches of their own; 0 = separate launches.
+                                        In the timing record nerf_mlp_bwd then excludes the dW sum and hashgrid_bwd includes both.
+                                        (Was `reserved`: callers that zero it keep the separate launches.) */
 } wisp_nerf_step_hyper;
 
 int64_t wisp_nerf_step_config_bytes(void);

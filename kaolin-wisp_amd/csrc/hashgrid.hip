@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "hashgrid_dev.h"
+#include "step_tail_dev.h"
 
 #define HG_TILE 64
 
@@ -768,6 +769,17 @@ struct AdamFlush {
 #define HG_TAIL_ROWS 8192
 #define WISP_WHOLE_LEVEL ((int64_t)1 << 62)               // covered_rows[l]: all rows of level l, whatever its spacing in first_idx
 struct TailLevels { int first_level, end_level, blocks; };
+// Side jobs (wisp_hashgrid_interpolate_bwd_adamw_tail): the two small sums that end the native training step's backward - the decoder's
+// dW partial rows into dec_grad and the loss partials into the loss slot, bodies in step_tail_dev.h - as `wgs` further workgroups at
+// the front of the reduce launch: index 0 the loss (when loss_wgs), then dw_wgs workgroups of 64 parameters each.  Their
+// inputs were written by launches in front of this one on the stream and nobody reads their outputs before the next launch, so the
+// kernel boundaries give all the ordering there is to give; they share nothing with the rest of the grid.
+struct StepTail {
+    const float* dw_partials; float* dec_grad; const float* loss_partials; float* loss;
+    int dw_rows, in_dim, loss_count; float inv_n;
+    int loss_wgs, dw_wgs, wgs;
+};
+static_assert(RD_THREADS == STEP_TAIL_THREADS, "the side jobs run in reduce workgroups");
 
 template <typename T, int F, typename ACC, bool ADAM>
 static __device__ __forceinline__ void
@@ -1065,7 +1077,7 @@ template <typename T, int F, bool ADAM>
 __global__ void __launch_bounds__(RD_THREADS)
 hashgrid_bwd_reduce_kernel(const int64_t* __restrict__ first_idx, LevelList levels, int chunk_shift, BinLevels bins,
                            uint32_t ntiles, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ records,
-                           float* __restrict__ grad_codebook, int extra_bits, AdamFlush ad, TailLevels tail) {
+                           float* __restrict__ grad_codebook, int extra_bits, AdamFlush ad, TailLevels tail, StepTail side) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rd_smem[];            // [chunk entries * F] accumulators
     __shared__ uint32_t s_wave_max[RD_THREADS / 64];
     if constexpr (ADAM) {
@@ -1073,8 +1085,17 @@ hashgrid_bwd_reduce_kernel(const int64_t* __restrict__ first_idx, LevelList leve
         // take the optimizer's step - weight decay moves them - and used to be why a separate optimizer launch streamed 2^19 rows.
         // tail.blocks extra workgroups of this launch do it instead: 8192 rows each, the gradient read from the table (zero
         // unless something else wrote there; put back to zero like the optimizer's fused zeroing), wisp_adamw_update as everywhere.
-        if (blockIdx.x < (unsigned)tail.blocks) {                // FIRST in dispatch order: short streaming workgroups that are gone
-            const int64_t k = (int64_t)blockIdx.x;               // before the record walks need the bandwidth (at the END of the grid
+        // side jobs and tail levels FIRST in dispatch order: short workgroups that are gone before the record walks need the CUs
+        if (blockIdx.x < (unsigned)side.wgs) {
+            float* lds = reinterpret_cast<float*>(rd_smem);      // (the launcher checked that the bucket accumulators are large enough)
+            const int w = (int)blockIdx.x - side.loss_wgs;
+            if (w < 0) wisp_tail::loss_sum(side.loss_partials, side.loss_count, side.inv_n, side.loss, (int)threadIdx.x, lds);
+            else wisp_tail::dw_reduce(side.dw_partials, side.dw_rows, side.in_dim, side.dec_grad, w, (int)threadIdx.x, lds);
+            return;
+        }
+        const unsigned tail_index = blockIdx.x - (unsigned)side.wgs;
+        if (tail_index < (unsigned)tail.blocks) {                // short streaming workgroups that are gone
+            const int64_t k = (int64_t)tail_index;               // before the record walks need the bandwidth (at the END of the grid
                                                                  // they lengthened the launch by their own 6 us)
             // EVERY row of the tail levels as the caller's first_idx lays them out - [first_idx[first_level], first_idx[end_level]) -
             // in pieces of HG_TAIL_ROWS dealt round-robin to the tail workgroups: the launcher sizes their number from
@@ -1098,7 +1119,7 @@ hashgrid_bwd_reduce_kernel(const int64_t* __restrict__ first_idx, LevelList leve
     }
     // flattened (level, bucket, split) grid
     // heaviest first: the fine (hashed) levels carry most of the records, the cheap coarse buckets fill the tail of the grid
-    const int bid = (int)(gridDim.x - 1u - blockIdx.x);          // (the tail workgroups took the first tail.blocks indices)
+    const int bid = (int)(gridDim.x - 1u - blockIdx.x);          // (side jobs and tail workgroups took the first indices)
     int li = 0;
     while (li + 1 < levels.n && bid >= bins.blk_base[li + 1]) ++li;
     const int splits = bins.splits[li];
@@ -1322,7 +1343,10 @@ template <typename T, int F, int DIM>
 static int launch_bwd(const float* coords, int64_t n, const void* grad_feats, const int64_t* first_idx,
                       const HashLevels& lv, int num_lods, uint32_t tsize, int zero_from_col, float* grad_codebook,
                       void* workspace, int64_t workspace_bytes, const float* cap_scale, hipStream_t s,
-                      const AdamFlush* adam = nullptr, int64_t* covered_rows = nullptr) {
+                      const AdamFlush* adam = nullptr, int64_t* covered_rows = nullptr, const StepTail* side_jobs = nullptr,
+                      int* side_done = nullptr) {
+    // side_jobs / side_done (host): see StepTail; *side_done = 1 when the jobs went with the reduce launch, else it stays as it
+    // is and the sums are the caller's to launch (no binned launch, or not the fused-optimizer form of it)
     // adam / covered_rows (host, [num_lods], zeroed by the caller): the optimizer folded into the reduce kernel's flush for the
     // levels whose buckets have ONE owner; covered_rows[l] = rows at the start of level l that were updated there
     const int pow2 = (tsize & (tsize - 1)) == 0;
@@ -1416,8 +1440,16 @@ static int launch_bwd(const float* coords, int64_t n, const void* grad_feats, co
     // that the binary point moves up with the sample count so that no sum can leave its 63 bits
     int extra_bits = 0;
     while (((int64_t)1 << (21 + extra_bits)) < n) ++extra_bits;
-    hipLaunchKernelGGL(rd, dim3(plan.total_blocks + tail.blocks), dim3(RD_THREADS), rd_lds, s, first_idx, active, plan.chunk_shift,
-                       plan.bins, (uint32_t)plan.ntiles, counts, records, grad_codebook, extra_bits, fused ? *adam : AdamFlush{}, tail);
+    StepTail side{};
+    if (fused && side_jobs && side_done && rd_lds >= sizeof(float) * STEP_TAIL_DW_LDS_FLOATS) {
+        side = *side_jobs;
+        side.loss_wgs = side.loss_partials && side.loss ? 1 : 0;
+        side.dw_wgs = side.dw_partials && side.dec_grad && side.dw_rows > 0 ? wisp_tail::DW_COL_BLOCKS : 0;
+        side.wgs = side.loss_wgs + side.dw_wgs;
+        *side_done = 1;
+    }
+    hipLaunchKernelGGL(rd, dim3(plan.total_blocks + tail.blocks + side.wgs), dim3(RD_THREADS), rd_lds, s, first_idx, active, plan.chunk_shift,
+                       plan.bins, (uint32_t)plan.ntiles, counts, records, grad_codebook, extra_bits, fused ? *adam : AdamFlush{}, tail, side);
     return 0;
 }
 
@@ -1488,14 +1520,15 @@ extern "C" int wisp_hashgrid_interpolate_bwd(const float* coords, int64_t n, int
 // per level, how many of its leading rows were updated in the flush; every other element of the table still has its gradient in
 // grad_codebook and is the caller's to update (wisp_adamw_step_groups).  Levels that were not binned, or whose buckets are split
 // over several workgroups (the coarse ones), report 0.
-extern "C" int wisp_hashgrid_interpolate_bwd_adamw(const float* coords, int64_t n, int coord_dim, const void* grad_feats,
-                                                   int dtype, int feature_dim, const int64_t* first_idx,
-                                                   const int32_t* resolutions, int num_lods, int codebook_bitwidth,
-                                                   int zero_from_col, float* grad_codebook, void* workspace,
-                                                   int64_t workspace_bytes, const float* level_cap_scale, float* param,
-                                                   float* exp_avg, float* exp_avg_sq, void* bf16_shadow, float lr, float beta1,
-                                                   float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
-                                                   int64_t* covered_rows, wisp_stream_t stream) {
+static int bwd_adamw_impl(const float* coords, int64_t n, int coord_dim, const void* grad_feats,
+                          int dtype, int feature_dim, const int64_t* first_idx,
+                          const int32_t* resolutions, int num_lods, int codebook_bitwidth,
+                          int zero_from_col, float* grad_codebook, void* workspace,
+                          int64_t workspace_bytes, const float* level_cap_scale, float* param,
+                          float* exp_avg, float* exp_avg_sq, void* bf16_shadow, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                          int64_t* covered_rows, const StepTail* side_jobs, int* side_done,
+                          wisp_stream_t stream) {
     WISP_REQUIRE(n >= 0, "negative n");
     WISP_REQUIRE(num_lods >= 1 && num_lods <= HG_MAX_LODS, "num_lods out of range");
     WISP_REQUIRE(covered_rows && param && exp_avg && exp_avg_sq && step >= 1, "optimizer arguments missing");
@@ -1513,9 +1546,45 @@ extern "C" int wisp_hashgrid_interpolate_bwd_adamw(const float* coords, int64_t 
                        1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step)), grad_scale};
     hipStream_t s = (hipStream_t)stream;
     HG_DISPATCH(launch_bwd, coords, n, grad_feats, first_idx, lv, num_lods, (uint32_t)tsize, zero_from_col,
-                grad_codebook, workspace, workspace_bytes, level_cap_scale, s, &ad, covered_rows)
+                grad_codebook, workspace, workspace_bytes, level_cap_scale, s, &ad, covered_rows, side_jobs, side_done)
     WISP_CHECK_LAUNCH();
     return WISP_OK;
+}
+
+extern "C" int wisp_hashgrid_interpolate_bwd_adamw(const float* coords, int64_t n, int coord_dim, const void* grad_feats,
+                                                   int dtype, int feature_dim, const int64_t* first_idx,
+                                                   const int32_t* resolutions, int num_lods, int codebook_bitwidth,
+                                                   int zero_from_col, float* grad_codebook, void* workspace,
+                                                   int64_t workspace_bytes, const float* level_cap_scale, float* param,
+                                                   float* exp_avg, float* exp_avg_sq, void* bf16_shadow, float lr, float beta1,
+                                                   float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                                                   int64_t* covered_rows, wisp_stream_t stream) {
+    return bwd_adamw_impl(coords, n, coord_dim, grad_feats, dtype, feature_dim, first_idx, resolutions, num_lods, codebook_bitwidth,
+                          zero_from_col, grad_codebook, workspace, workspace_bytes, level_cap_scale, param, exp_avg, exp_avg_sq, bf16_shadow,
+                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, nullptr, nullptr, stream);
+}
+
+// The same with the step's two closing sums riding in the reduce launch (StepTail).  *tail_done (host): 1 when they did; 0 when
+// the launch that carries them did not happen (fewer than 4096 samples, a workspace too small to bin, not a two-feature table) -
+// the sums are then the caller's to launch: wisp_nerf_mlp_reduce_partials, wisp_loss_sum.
+extern "C" int wisp_hashgrid_interpolate_bwd_adamw_tail(const float* coords, int64_t n, int coord_dim, const void* grad_feats,
+                                                        int dtype, int feature_dim, const int64_t* first_idx,
+                                                        const int32_t* resolutions, int num_lods, int codebook_bitwidth,
+                                                        int zero_from_col, float* grad_codebook, void* workspace,
+                                                        int64_t workspace_bytes, const float* level_cap_scale, float* param,
+                                                        float* exp_avg, float* exp_avg_sq, void* bf16_shadow, float lr, float beta1,
+                                                        float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                                                        int64_t* covered_rows, const wisp_step_tail* tail, int* tail_done,
+                                                        wisp_stream_t stream) {
+    WISP_REQUIRE(tail && tail_done, "side-job descriptor missing");
+    WISP_REQUIRE(tail->dw_rows >= 0 && tail->loss_count >= 0 && tail->in_dim >= 1 && tail->in_dim <= wisp_mlp::IN, "side-job descriptor out of range");
+    *tail_done = 0;
+    StepTail side{};
+    side.dw_partials = tail->dw_partials; side.dec_grad = tail->dec_grad; side.dw_rows = tail->dw_rows; side.in_dim = tail->in_dim;
+    side.loss_partials = tail->loss_partials; side.loss = tail->loss; side.loss_count = tail->loss_count; side.inv_n = tail->inv_n;
+    return bwd_adamw_impl(coords, n, coord_dim, grad_feats, dtype, feature_dim, first_idx, resolutions, num_lods, codebook_bitwidth,
+                          zero_from_col, grad_codebook, workspace, workspace_bytes, level_cap_scale, param, exp_avg, exp_avg_sq, bf16_shadow,
+                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, &side, tail_done, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- gradient w.r.t. the coordinates

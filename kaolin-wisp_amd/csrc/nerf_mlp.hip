@@ -23,6 +23,7 @@
 #include "wisp_common.h"
 #include "nerf_mlp_shape.h"
 #include "nerf_mlp_f32_dev.h"
+#include "step_tail_dev.h"
 #include <cstdlib>
 
 namespace {
@@ -372,24 +373,12 @@ nerf_mlp_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, i
 }
 
 // grad_params[packed(j)] += sum over partial rows (rows are in canonical order, nerf_mlp_shape.h).
-// Block = 64 parameters x 16 row groups (row-strided partial sums, then LDS).
-__global__ void __launch_bounds__(1024)
+// Block = 64 parameters x 16 row groups (row-strided partial sums, then LDS): wisp_tail::dw_reduce, step_tail_dev.h - the same
+// body runs as side workgroups of the hash-grid reduce launch in the native training step.
+__global__ void __launch_bounds__(STEP_TAIL_THREADS)
 nerf_mlp_reduce_kernel(const float* __restrict__ partials, int rows, int in_dim, float* __restrict__ grad_params) {
-    __shared__ float s[16][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + tx;
-    float a = 0.0f;
-    if (j < NPARAM)
-        for (int r = ty; r < rows; r += 16) a += partials[(int64_t)r * NPARAM_PAD + j];
-    s[ty][tx] = a;
-    __syncthreads();
-    if (ty == 0 && j < NPARAM) {
-        float t = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += s[k][tx];
-        const int dst = packed_index(j, in_dim);
-        if (dst >= 0) grad_params[dst] += t;
-    }
+    __shared__ float s[STEP_TAIL_DW_LDS_FLOATS];
+    wisp_tail::dw_reduce(partials, rows, in_dim, grad_params, (int)blockIdx.x, (int)threadIdx.x, s);
 }
 
 int cu_count() {
@@ -541,22 +530,45 @@ extern "C" int wisp_nerf_mlp_fwd_rays(const void* feats, int dtype_io, const voi
     return WISP_OK;
 }
 
+// chain kernel only: the partial rows stay in `workspace` ([*partial_rows][NPARAM_PAD]) for the caller to sum into grad_params -
+// wisp_nerf_mlp_reduce_partials, or the side workgroups of wisp_hashgrid_interpolate_bwd_adamw_tail
+extern "C" int wisp_nerf_mlp_bwd_rays_partials(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx,
+                                               int64_t num_samples, int in_dim, int hidden, int view_freqs, const float* params,
+                                               const float* grad_rgb, const float* grad_density, void* grad_feats,
+                                               float* workspace, int64_t workspace_bytes, int* partial_rows, wisp_stream_t stream) {
+    WISP_REQUIRE(num_samples >= 0 && partial_rows, "bad arguments");
+    *partial_rows = 0;
+    if (int rc = check_rays_shape(in_dim, hidden, view_freqs, dtype_io)) return rc;
+    if (num_samples == 0) return WISP_OK;
+    WISP_REQUIRE(feats && dir_code && ridx && params && grad_rgb && grad_density && grad_feats && workspace, "null pointer");
+    WISP_REQUIRE(workspace_bytes >= wisp_nerf_mlp_bwd_workspace_bytes(num_samples, hidden), "workspace too small (wisp_nerf_mlp_bwd_workspace_bytes)");
+    if (int rc = wisp_mlp::bf16_backward_rays(feats, dtype_io, dir_code, ridx, num_samples, in_dim, params, grad_rgb, grad_density, grad_feats,
+                                              workspace, partial_rows, (hipStream_t)stream))
+        return rc;
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
+extern "C" int wisp_nerf_mlp_reduce_partials(const float* workspace, int partial_rows, int in_dim, float* grad_params, wisp_stream_t stream) {
+    WISP_REQUIRE(partial_rows >= 0 && in_dim >= 1 && in_dim <= IN, "bad arguments");
+    if (partial_rows == 0) return WISP_OK;
+    WISP_REQUIRE(workspace && grad_params, "null pointer");
+    hipLaunchKernelGGL(nerf_mlp_reduce_kernel, dim3((NPARAM + 63) / 64), dim3(1024), 0, (hipStream_t)stream, workspace, partial_rows, in_dim, grad_params);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
 extern "C" int wisp_nerf_mlp_bwd_rays(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx,
                                       int64_t num_samples, int in_dim, int hidden, int view_freqs, const float* params,
                                       const float* grad_rgb, const float* grad_density, void* grad_feats, float* grad_params,
                                       float* workspace, int64_t workspace_bytes, wisp_stream_t stream) {
     WISP_REQUIRE(num_samples >= 0, "negative count");
-    if (int rc = check_rays_shape(in_dim, hidden, view_freqs, dtype_io)) return rc;
-    if (num_samples == 0) return WISP_OK;
-    WISP_REQUIRE(feats && dir_code && ridx && params && grad_rgb && grad_density && grad_feats && grad_params && workspace, "null pointer");
-    WISP_REQUIRE(workspace_bytes >= wisp_nerf_mlp_bwd_workspace_bytes(num_samples, hidden), "workspace too small (wisp_nerf_mlp_bwd_workspace_bytes)");
+    if (num_samples > 0) WISP_REQUIRE(grad_params, "null pointer");
     int rows = 0;
-    if (int rc = wisp_mlp::bf16_backward_rays(feats, dtype_io, dir_code, ridx, num_samples, in_dim, params, grad_rgb, grad_density, grad_feats,
-                                              workspace, &rows, (hipStream_t)stream))
+    if (int rc = wisp_nerf_mlp_bwd_rays_partials(feats, dtype_io, dir_code, ridx, num_samples, in_dim, hidden, view_freqs, params, grad_rgb,
+                                                 grad_density, grad_feats, workspace, workspace_bytes, &rows, stream))
         return rc;
-    hipLaunchKernelGGL(nerf_mlp_reduce_kernel, dim3((NPARAM + 63) / 64), dim3(1024), 0, (hipStream_t)stream, workspace, rows, in_dim, grad_params);
-    WISP_CHECK_LAUNCH();
-    return WISP_OK;
+    return wisp_nerf_mlp_reduce_partials(workspace, rows, in_dim, grad_params, stream);
 }
 
 // ---- the per-ray kernels with prebuilt operand images (hidden 64, bf16 compute) -----------------------------------------------
@@ -590,20 +602,32 @@ extern "C" int wisp_nerf_mlp_fwd_rays_img(const void* feats, int dtype_io, const
     return WISP_OK;
 }
 
+extern "C" int wisp_nerf_mlp_bwd_rays_img_partials(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx,
+                                                   int64_t num_samples, int in_dim, int hidden, int view_freqs, const float* params,
+                                                   const void* image, const float* grad_rgb, const float* grad_density, void* grad_feats,
+                                                   float* workspace, int64_t workspace_bytes, int* partial_rows, wisp_stream_t stream) {
+    WISP_REQUIRE(num_samples >= 0 && partial_rows, "bad arguments");
+    *partial_rows = 0;
+    if (int rc = check_rays_shape(in_dim, hidden, view_freqs, dtype_io)) return rc;
+    if (num_samples == 0) return WISP_OK;
+    WISP_REQUIRE(feats && dir_code && ridx && params && image && grad_rgb && grad_density && grad_feats && workspace, "null pointer");
+    WISP_REQUIRE(workspace_bytes >= wisp_nerf_mlp_bwd_workspace_bytes(num_samples, hidden), "workspace too small (wisp_nerf_mlp_bwd_workspace_bytes)");
+    if (int rc = wisp_mlp::bf16_backward_rays_img(feats, dtype_io, dir_code, ridx, num_samples, in_dim, image, grad_rgb, grad_density,
+                                                  grad_feats, workspace, partial_rows, (hipStream_t)stream))
+        return rc;
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
 extern "C" int wisp_nerf_mlp_bwd_rays_img(const void* feats, int dtype_io, const void* dir_code, const int64_t* ridx,
                                           int64_t num_samples, int in_dim, int hidden, int view_freqs, const float* params,
                                           const void* image, const float* grad_rgb, const float* grad_density, void* grad_feats,
                                           float* grad_params, float* workspace, int64_t workspace_bytes, wisp_stream_t stream) {
     WISP_REQUIRE(num_samples >= 0, "negative count");
-    if (int rc = check_rays_shape(in_dim, hidden, view_freqs, dtype_io)) return rc;
-    if (num_samples == 0) return WISP_OK;
-    WISP_REQUIRE(feats && dir_code && ridx && params && image && grad_rgb && grad_density && grad_feats && grad_params && workspace, "null pointer");
-    WISP_REQUIRE(workspace_bytes >= wisp_nerf_mlp_bwd_workspace_bytes(num_samples, hidden), "workspace too small (wisp_nerf_mlp_bwd_workspace_bytes)");
+    if (num_samples > 0) WISP_REQUIRE(grad_params, "null pointer");
     int rows = 0;
-    if (int rc = wisp_mlp::bf16_backward_rays_img(feats, dtype_io, dir_code, ridx, num_samples, in_dim, image, grad_rgb, grad_density,
-                                                  grad_feats, workspace, &rows, (hipStream_t)stream))
+    if (int rc = wisp_nerf_mlp_bwd_rays_img_partials(feats, dtype_io, dir_code, ridx, num_samples, in_dim, hidden, view_freqs, params, image,
+                                                     grad_rgb, grad_density, grad_feats, workspace, workspace_bytes, &rows, stream))
         return rc;
-    hipLaunchKernelGGL(nerf_mlp_reduce_kernel, dim3((NPARAM + 63) / 64), dim3(1024), 0, (hipStream_t)stream, workspace, rows, in_dim, grad_params);
-    WISP_CHECK_LAUNCH();
-    return WISP_OK;
+    return wisp_nerf_mlp_reduce_partials(workspace, rows, in_dim, grad_params, stream);
 }

@@ -9,6 +9,7 @@
 // fused into the same kernel.
 #include "wisp_common.h"
 #include "raygen_dev.h"
+#include "step_tail_dev.h"
 
 // Wave-wide inclusive scan / sum on the VALU (DPP), no LDS traffic: Hillis-Steele inside each 16-lane row (row_shr 1, 2, 4, 8),
 // then the row totals travel with row_bcast:15 (into rows 1 and 3) and row_bcast:31 (into rows 2 and 3).  Lanes without a
@@ -468,27 +469,19 @@ rgb_loss_kernel(const float* __restrict__ rgb, const float* __restrict__ gt, int
     if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-__global__ void __launch_bounds__(1024)
+// one workgroup adds the partials in a fixed order: wisp_tail::loss_sum, step_tail_dev.h (the same body runs as a side workgroup of the
+// hash-grid reduce launch in the native training step)
+__global__ void __launch_bounds__(STEP_TAIL_THREADS)
 loss_sum_kernel(const float* __restrict__ partial, int n, float inv_n, float* __restrict__ loss) {
-    __shared__ float part[16];
-    float t = 0.0f;
-    for (int base = 0; base < n; base += 8 * 1024) {      // eight loads of a thread in flight at once
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { const int i = base + threadIdx.x + k * 1024; v[k] = i < n ? partial[i] : 0.0f; }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t += v[k];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) s += part[w];
-        loss[0] = s * inv_n;
-    }
+    __shared__ float part[STEP_TAIL_LOSS_LDS_FLOATS];
+    wisp_tail::loss_sum(partial, n, inv_n, loss, (int)threadIdx.x, part);
+}
+
+extern "C" int wisp_loss_sum(const float* partials, int num_partials, float inv_n, float* loss, wisp_stream_t stream) {
+    WISP_REQUIRE(partials && num_partials >= 0 && loss, "bad arguments");
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partials, num_partials, inv_n, loss);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
 }
 
 extern "C" int wisp_rgb_loss(const float* rgb, const float* gt, int64_t num_elements, int kind, float* grad, float* loss,
@@ -966,11 +959,13 @@ composite_loss_split_kernel(const float* __restrict__ color, const float* __rest
     }
 }
 
-extern "C" int wisp_composite_loss(const float* color, const float* density, const float* deltas, const int64_t* ray_offsets,
-                                   int64_t num_rays, int64_t num_samples, const float* bg, const float* gt, int kind,
-                                   float* grad_color, float* grad_density, float* out_rgb, float* loss, float* workspace,
-                                   int64_t workspace_floats, wisp_stream_t stream) {
-    WISP_REQUIRE(num_rays > 0 && num_samples >= 0 && bg && gt && ray_offsets && loss && workspace && workspace_floats >= 1, "bad arguments");
+// the compositing launch only: workspace[0 .. *num_partials) holds the loss partials, loss = (their sum in index order) * *inv_n is
+// the caller's to form - wisp_loss_sum, or the side workgroup of wisp_hashgrid_interpolate_bwd_adamw_tail
+extern "C" int wisp_composite_loss_partials(const float* color, const float* density, const float* deltas, const int64_t* ray_offsets,
+                                            int64_t num_rays, int64_t num_samples, const float* bg, const float* gt, int kind,
+                                            float* grad_color, float* grad_density, float* out_rgb, float* workspace,
+                                            int64_t workspace_floats, int* num_partials, float* inv_n_out, wisp_stream_t stream) {
+    WISP_REQUIRE(num_rays > 0 && num_samples >= 0 && bg && gt && ray_offsets && workspace && workspace_floats >= 1 && num_partials && inv_n_out, "bad arguments");
     WISP_REQUIRE(kind >= 0 && kind <= 2, "kind: 0 huber, 1 l2, 2 l1");
     WISP_REQUIRE(num_samples == 0 || (color && density && deltas && grad_color && grad_density), "null pointer");
     const Bg b{bg[0], bg[1], bg[2]};
@@ -994,7 +989,21 @@ extern "C" int wisp_composite_loss(const float* color, const float* density, con
     else
         hipLaunchKernelGGL(composite_loss_kernel<4>, dim3((groups + 3) / 4), dim3(256), 0, (hipStream_t)stream, color, density, deltas, ray_offsets,
                            num_rays, groups, b, gt, kind, inv_n, grad_color, grad_density, out_rgb, workspace);
-    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, workspace, groups, inv_n, loss);
+    *num_partials = groups;
+    *inv_n_out = inv_n;
     WISP_CHECK_LAUNCH();
     return WISP_OK;
+}
+
+extern "C" int wisp_composite_loss(const float* color, const float* density, const float* deltas, const int64_t* ray_offsets,
+                                   int64_t num_rays, int64_t num_samples, const float* bg, const float* gt, int kind,
+                                   float* grad_color, float* grad_density, float* out_rgb, float* loss, float* workspace,
+                                   int64_t workspace_floats, wisp_stream_t stream) {
+    WISP_REQUIRE(loss, "bad arguments");
+    int groups = 0;
+    float inv_n = 0.0f;
+    if (int rc = wisp_composite_loss_partials(color, density, deltas, ray_offsets, num_rays, num_samples, bg, gt, kind, grad_color, grad_density,
+                                              out_rgb, workspace, workspace_floats, &groups, &inv_n, stream))
+        return rc;
+    return wisp_loss_sum(workspace, groups, inv_n, loss, stream);
 }

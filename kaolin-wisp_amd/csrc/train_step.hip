@@ -302,21 +302,57 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
     else
         NS_CALL(wisp_nerf_mlp_fwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, color, density, st));
     NS_MARK(3);
-    NS_CALL(wisp_composite_loss(color, density, deltas, m.offsets, R, S, c.bg, gts, c.loss_kind, g_color, g_density, nullptr, loss_slot,
-                                at<float>(s, s->lay.comp_ws), s->lay.comp_ws_floats, st));
+    // The step's two closing sums - the loss partials into the loss slot, the decoder's dW partial rows into dec_grad - are launches
+    // of their own (inside wisp_composite_loss / wisp_nerf_mlp_bwd_rays*), or with hp->tail_fold side workgroups of the hash-grid reduce
+    // launch (wisp_step_tail): nothing reads either result before the optimizer launch behind it.
+    const bool fold = hp->optimizer == 2 && c.table_param && c.table_exp_avg && c.table_exp_avg_sq;
+    const bool tail_fold = fold && hp->tail_fold != 0;
+    wisp_step_tail tail{};
+    tail.in_dim = c.in_dim;
+    float* comp_ws = at<float>(s, s->lay.comp_ws);
+    float* mlp_ws = at<float>(s, s->lay.mlp_ws);
+    if (tail_fold) {
+        NS_CALL(wisp_composite_loss_partials(color, density, deltas, m.offsets, R, S, c.bg, gts, c.loss_kind, g_color, g_density, nullptr,
+                                             comp_ws, s->lay.comp_ws_floats, &tail.loss_count, &tail.inv_n, st));
+        tail.loss_partials = comp_ws;
+        tail.loss = loss_slot;
+    } else {
+        NS_CALL(wisp_composite_loss(color, density, deltas, m.offsets, R, S, c.bg, gts, c.loss_kind, g_color, g_density, nullptr, loss_slot,
+                                    comp_ws, s->lay.comp_ws_floats, st));
+    }
     // ---- backward
     NS_MARK(4);
-    if (image)
+    if (tail_fold) {
+        if (image)
+            NS_CALL(wisp_nerf_mlp_bwd_rays_img_partials(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, image,
+                                                        g_color, g_density, g_feats, mlp_ws, s->lay.mlp_ws_bytes, &tail.dw_rows, st));
+        else
+            NS_CALL(wisp_nerf_mlp_bwd_rays_partials(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, g_color,
+                                                    g_density, g_feats, mlp_ws, s->lay.mlp_ws_bytes, &tail.dw_rows, st));
+        tail.dw_partials = mlp_ws;
+        tail.dec_grad = c.dec_grad;
+    } else if (image) {
         NS_CALL(wisp_nerf_mlp_bwd_rays_img(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, image, g_color,
-                                           g_density, g_feats, c.dec_grad, at<float>(s, s->lay.mlp_ws), s->lay.mlp_ws_bytes, st));
-    else
+                                           g_density, g_feats, c.dec_grad, mlp_ws, s->lay.mlp_ws_bytes, st));
+    } else {
         NS_CALL(wisp_nerf_mlp_bwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, g_color, g_density,
-                                       g_feats, c.dec_grad, at<float>(s, s->lay.mlp_ws), s->lay.mlp_ws_bytes, st));
+                                       g_feats, c.dec_grad, mlp_ws, s->lay.mlp_ws_bytes, st));
+    }
     NS_MARK(5);
     int64_t covered[16] = {0};
-    const bool fold = hp->optimizer == 2 && c.table_param && c.table_exp_avg && c.table_exp_avg_sq;
     NS_MARK(6);
-    if (fold)
+    if (tail_fold) {
+        int tail_done = 0;
+        NS_CALL(wisp_hashgrid_interpolate_bwd_adamw_tail(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
+                                                         c.num_lods, c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace,
+                                                         hashgrid_workspace_bytes, level_cap_scale, c.table_param, c.table_exp_avg,
+                                                         c.table_exp_avg_sq, c.table_shadow, hp->lr_grid, hp->beta1, hp->beta2, hp->eps,
+                                                         hp->weight_decay, hp->step, hp->grad_scale, covered, &tail, &tail_done, st));
+        if (!tail_done) {                              // no binned reduce launch (a tiny batch, a workspace too small): the old launches
+            NS_CALL(wisp_nerf_mlp_reduce_partials(tail.dw_partials, tail.dw_rows, tail.in_dim, tail.dec_grad, st));
+            NS_CALL(wisp_loss_sum(tail.loss_partials, tail.loss_count, tail.inv_n, tail.loss, st));
+        }
+    } else if (fold)
         NS_CALL(wisp_hashgrid_interpolate_bwd_adamw(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
                                                     c.num_lods, c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace,
                                                     hashgrid_workspace_bytes, level_cap_scale, c.table_param, c.table_exp_avg,

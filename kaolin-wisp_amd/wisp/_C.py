@@ -35,6 +35,8 @@ SIGNATURES = {
     "wisp_hashgrid_interpolate_bwd": [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp],
     "wisp_hashgrid_interpolate_bwd_adamw": [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp,
                                             c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp, c_vp],
+    "wisp_hashgrid_interpolate_bwd_adamw_tail": [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp,
+                                                 c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp],
     "wisp_hashgrid_grad_coords": [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     "wisp_hashgrid_bwd_workspace_bytes": [c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp],
     "wisp_hashgrid_bwd_slot_stats": [c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp],
@@ -112,6 +114,8 @@ SIGNATURES = {
     "wisp_adamw_step_groups": [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_i64, c_f32, c_i32, c_vp],
     "wisp_gather_rows": [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp],
     "wisp_composite_loss": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "wisp_composite_loss_partials": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "wisp_loss_sum": [c_vp, c_i32, c_f32, c_vp, c_vp],
     "wisp_rgb_loss": [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp],
     "wisp_generate_rays": [c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_composite_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -130,6 +134,9 @@ SIGNATURES = {
     "wisp_nerf_mlp_bwd_rays_img": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_nerf_mlp_fwd_rays": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_bwd_rays": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "wisp_nerf_mlp_bwd_rays_partials": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
+    "wisp_nerf_mlp_bwd_rays_img_partials": [c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp],
+    "wisp_nerf_mlp_reduce_partials": [c_vp, c_i32, c_i32, c_vp, c_vp],
     "wisp_nerf_mlp_bwd_workspace_bytes": [c_i64, c_i32],
     "wisp_nerf_mlp_workspace_floats": [],
     "wisp_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_i32, c_vp, c_vp],
@@ -199,7 +206,13 @@ class NerfStepHyper(ctypes.Structure):
     """include/wisp_hip.h: wisp_nerf_step_hyper."""
     _fields_ = ([("struct_bytes", c_i64), ("step", c_i64)]
                 + [(n, c_f32) for n in ("lr_decoder", "lr_grid", "lr_rest", "weight_decay", "beta1", "beta2", "eps", "grad_scale")]
-                + [("optimizer", c_i32), ("reserved", c_i32)])
+                + [("optimizer", c_i32), ("tail_fold", c_i32)])
+
+
+class StepTail(ctypes.Structure):
+    """include/wisp_hip.h: wisp_step_tail."""
+    _fields_ = ([(n, c_vp) for n in ("dw_partials", "dec_grad", "loss_partials", "loss")]
+                + [(n, c_i32) for n in ("dw_rows", "in_dim", "loss_count")] + [("inv_n", c_f32)])
 
 
 if ctypes.sizeof(NerfStepConfig) != lib.wisp_nerf_step_config_bytes():

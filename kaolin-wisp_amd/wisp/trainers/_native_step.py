@@ -14,6 +14,9 @@ import numpy as np
 import torch
 
 ENABLED = os.environ.get("WISP_NATIVE_STEP", "1") != "0"
+# WISP_STEP_TAIL_FOLD=0: the decoder's dW sum and the loss sum stay launches of their own instead of riding in the hash-grid reduce
+# launch (wisp_nerf_step_hyper.tail_fold; same bits either way)
+TAIL_FOLD = os.environ.get("WISP_STEP_TAIL_FOLD", "1") != "0"
 
 
 def _hip():
@@ -189,6 +192,7 @@ class NativeHashStep:
         hp.weight_decay, hp.beta1, hp.beta2, hp.eps = t.weight_decay, t.betas[0], t.betas[1], t.eps
         hp.grad_scale = 1.0 / t.world
         hp.optimizer = 2 if t.fuse_grid_optimizer else 1
+        hp.tail_fold = 1 if TAIL_FOLD else 0
         return hp
 
     def _hashgrid_scratch(self, dev, n_guess):
@@ -272,6 +276,7 @@ class NativeHashStep:
             cover = [min(int(cov[l]), first[l + 1] - first[l]) for l in range(L)]
             ga, gb = t.flat.ranges["grid"]
             t.fused_elements_last = 2 * sum(max(0, c) for c in cover)
+            self.covered_last = cover
         else:
             t.fused_elements_last = 0
         t.flat.mark_shadow_current()
