@@ -470,6 +470,18 @@ BIG_SPECS = [
     ("big f32 F2 extra bit", dict(dim=3, res=(32, 128), bw=16, F=2, dtype="f32", n=(1 << 21) + 65, gmax=1, claims=("multi_bucket", "hashed"))),
 ]
 BIG_NAMES = [s[0] for s in BIG_SPECS]
+# For the AdamW step folded into the reduce kernel's flush (tests/test_gpu_optim_exact.py; claims verified by
+# tests/test_optim_exact_host.py).  The fold exists for F = 2 and covers a level whose buckets have ONE reduce workgroup each: with
+# 5 emitting pieces that takes more than 32 buckets of 8192 rows, i.e. 2^19 rows or more.  2-D: res 512 is dense with 32 buckets
+# (split: not covered); res 1024 is dense at bitwidth 21 (128 buckets of strips, one owner) and hashed at bitwidth 19 (64 buckets,
+# one owner).
+ADAM_SPECS = [
+    ("adam dense one owner f32 F2 2d n5000", dict(dim=2, res=(512, 1024), bw=21, F=2, dtype="f32", n=5000, pad=(3, 2), claims=("dense", "multi_bucket", "split", "odd_start"))),
+    ("adam hashed one owner f32 F2 2d n5000", dict(dim=2, res=(512, 1024), bw=19, F=2, dtype="f32", n=5000, claims=("dense", "hashed", "one_owner", "split"))),
+    ("adam dead suffix bf16 F2 2d n5000", dict(dim=2, res=(512, 1024, 512), bw=19, F=2, dtype="bf16", n=5000, pad=(1, 2, 0), zero_from_col=4,
+                                               claims=("dead_levels", "hashed", "one_owner", "compact", "odd_start"))),
+]
+ADAM_NAMES = [s[0] for s in ADAM_SPECS]
 LOSS_SCALES = (16, 24, -30)
 LOSS_NAMES = ("generic f32 F2 n5000", "compact bf16 F2 3d n5000", "compact f16 F2 3d n8193", "generic f16 F4 n5000")
 F16_UNIT_EXP = -10                  # fp16 cannot hold 2^16: its loss-scale cases start from integers times 2^-10
@@ -480,7 +492,7 @@ _cases = {}
 
 def bwd_case(name):
     if name not in _cases:
-        spec = dict(dict(_BWD_SPECS + BIG_SPECS)[name])
+        spec = dict(dict(_BWD_SPECS + BIG_SPECS + ADAM_SPECS)[name])
         _cases[name] = _bwd(name, spec.pop("dim"), spec.pop("res"), spec.pop("bw"), spec.pop("F"), spec.pop("dtype"), spec.pop("n"),
                             spec.pop("claims"), **spec)
     return _cases[name]
