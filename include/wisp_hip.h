@@ -43,7 +43,7 @@ const char* wisp_last_error(void);
  * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step,
  * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_composite_loss_partials, wisp_loss_sum,
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
- * wisp_hashgrid_interpolate_bwd_adamw_tail - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -235,6 +235,19 @@ int wisp_spc_raytrace_emit(const uint8_t* octree, const int16_t* points, const i
                            const float* origins, const float* dirs, int64_t num_rays, int level,
                            const int64_t* offsets, int with_exit, const float* cache, int cache_cap,
                            int32_t* ridx, int32_t* pidx, float* depth, wisp_stream_t stream);
+
+/* First ray / cell intersection at `level` only: one row per ray in ONE launch (replaces the raytrace -> mark_pack_boundaries ->
+ * four gathers / scatters of wisp/tracers/packed_spc_tracer.py:56-90, and with `colors` also SPCField.rgba,
+ * wisp/models/nefs/spc_field.py:141-147).  Same traversal and float order as wisp_spc_raytrace_*: pidx[r] / depth[r] are the
+ * first nugget of ray r bit for bit, or -1 / 0 when the ray has none.  level 0..15, num_rays < 2^31.
+ * colors (optional, f32 [cells of `level`, color_stride], color_stride >= 3; needs rgb and level_first = pyramid[1, level], the
+ * point-hierarchy index of the level's first cell): rgb[r] = colors[pidx[r] - level_first, 0:3], zeros on a miss.
+ * rgb [R,3], alpha [R] (1 / 0), hit [R] (1 / 0) are optional.  Every row of every output given is written for every ray;
+ * nothing needs to be cleared by the caller. */
+int wisp_spc_first_hit(const uint8_t* octree, const int16_t* points, const int32_t* exsum,
+                       const float* origins, const float* dirs, int64_t num_rays, int level,
+                       const float* colors, int color_stride, int32_t level_first,
+                       int32_t* pidx, float* depth, float* rgb, float* alpha, uint8_t* hit, wisp_stream_t stream);
 
 int wisp_mark_pack_boundaries_i64(const int64_t* ids, int64_t n, uint8_t* boundary, wisp_stream_t stream);
 int wisp_mark_pack_boundaries_i32(const int32_t* ids, int64_t n, uint8_t* boundary, wisp_stream_t stream);

@@ -417,6 +417,136 @@ extern "C" int wisp_spc_raytrace_emit(const uint8_t* octree, const int16_t* poin
     return WISP_OK;
 }
 
+// ---- first hit only.  The SPC tracer (wisp/tracers/packed_spc_tracer.py:56-66) asks for every nugget and keeps the first of
+// each ray; here the walk of spc_raytrace8_kernel - same 8 lanes per ray, same i XOR code lane order, same LDS stack of
+// pending siblings, same slab_test, hence the same pidx and the same depth bits as the first nugget of that kernel - stops at
+// the first leaf-parent step whose hit mask is not empty.  One row per ray: no count / scan / emit, nothing read back.  The
+// lane that owns the lowest set bit of the mask writes the ray's rows; a ray that exhausts the tree or misses the root has
+// its miss rows written by lane 0 of the group, so every requested row is written exactly once and nothing needs zeroing.
+__global__ void __launch_bounds__(RT8_RAYS * 8)
+spc_first_hit_kernel(const uint8_t* __restrict__ octree, const int16_t* __restrict__ points,
+                     const int32_t* __restrict__ exsum, const float* __restrict__ origins,
+                     const float* __restrict__ dirs, int64_t num_rays, int level, const float* __restrict__ colors,
+                     int color_stride, int32_t level_first, int32_t* __restrict__ out_pidx, float* __restrict__ out_depth,
+                     float* __restrict__ out_rgb, float* __restrict__ out_alpha, uint8_t* __restrict__ out_hit) {
+    __shared__ int32_t s_base[RT_MAX_LEVEL][RT8_RAYS];
+    __shared__ uint32_t s_st[RT_MAX_LEVEL][RT8_RAYS];        // pending hit mask (8b) | code (3b) << 8 | child bits (8b) << 16
+    const int g = threadIdx.x >> 3, sub = threadIdx.x & 7;
+    const int shift = (threadIdx.x & 63) & ~7;               // position of this group's 8 bits inside the wave ballot
+    const int64_t r = (int64_t)blockIdx.x * RT8_RAYS + g;
+    const bool in_range = r < num_rays;
+    bool active = in_range;
+    float ox = 0.f, oy = 0.f, oz = 0.f, ix = 0.f, iy = 0.f, iz = 0.f;
+    if (active) {
+        ox = origins[r * 3]; oy = origins[r * 3 + 1]; oz = origins[r * 3 + 2];
+        ix = __fdiv_rn(1.0f, dirs[r * 3]); iy = __fdiv_rn(1.0f, dirs[r * 3 + 1]); iz = __fdiv_rn(1.0f, dirs[r * 3 + 2]);
+    }
+    int32_t res_pidx = -1;                                   // >= 0 on the one lane that writes the ray's hit rows
+    float res_depth = 0.0f;
+    bool found = false;                                      // group-uniform
+    int l = 0;
+    uint32_t bits = 0, code = 0;
+    int32_t base = 0;
+    if (active) {
+        const Slab s = slab_test(ox, oy, oz, ix, iy, iz, 0, 0, 0, 0);
+        if (!s.hit) active = false;
+        else if (level == 0) {
+            found = true;
+            if (sub == 0) { res_pidx = 0; res_depth = s.entry; }
+            active = false;
+        } else {
+            code = ((ox > s.cx) ? 4u : 0u) | ((oy > s.cy) ? 2u : 0u) | ((oz > s.cz) ? 1u : 0u);
+            bits = octree[0];
+            base = exsum[0];
+        }
+    }
+    while (__any(active)) {
+        // ---- test the 8 children of the current node (depth l -> l + 1)
+        bool hit = false;
+        float entry = 0.0f;
+        int32_t child = 0;
+        if (active) {
+            const uint32_t j = (uint32_t)sub ^ code;
+            if ((bits >> j) & 1u) {
+                child = base + __popc(bits & ((2u << j) - 1u));
+                const int16_t* pt = points + (int64_t)child * 3;
+                const Slab c = slab_test(ox, oy, oz, ix, iy, iz, pt[0], pt[1], pt[2], l + 1);
+                hit = c.hit;
+                entry = c.entry;
+            }
+        }
+        uint32_t mask = (uint32_t)(__ballot(hit) >> shift) & 0xffu;
+        if (active) {
+            if (l + 1 == level && mask != 0u) {                // leaf parent: the lowest set lane is the ray's first nugget
+                found = true;
+                active = false;
+                if ((uint32_t)sub == (uint32_t)__builtin_ctz(mask)) { res_pidx = child; res_depth = entry; }
+            }
+        }
+        if (active) {
+            // ---- next node: first pending child here, else back up
+            while (mask == 0u && l > 0) {
+                --l;
+                const uint32_t st = s_st[l][g];
+                mask = st & 0xffu; code = (st >> 8) & 7u; bits = st >> 16;
+                base = s_base[l][g];
+            }
+            if (mask == 0u) active = false;
+            else {
+                const uint32_t i0 = (uint32_t)__builtin_ctz(mask);
+                mask &= mask - 1u;
+                s_st[l][g] = mask | (code << 8) | (bits << 16);      // all 8 lanes write the same value
+                s_base[l][g] = base;
+                const uint32_t j0 = i0 ^ code;
+                const int32_t node = base + __popc(bits & ((2u << j0) - 1u));
+                ++l;
+                bits = octree[node];
+                base = exsum[node];
+                const int16_t* pt = points + (int64_t)node * 3;
+                const float rr = 1.0f / (float)(1 << l);
+                const float cx = rr * (2.0f * (float)pt[0] + 1.0f) - 1.0f, cy = rr * (2.0f * (float)pt[1] + 1.0f) - 1.0f,
+                            cz = rr * (2.0f * (float)pt[2] + 1.0f) - 1.0f;
+                code = ((ox > cx) ? 4u : 0u) | ((oy > cy) ? 2u : 0u) | ((oz > cz) ? 1u : 0u);
+            }
+        }
+    }
+    if (!in_range) return;
+    if (res_pidx >= 0) {
+        out_pidx[r] = res_pidx;
+        out_depth[r] = res_depth;
+        if (out_rgb) {
+            const float* row = colors + (int64_t)(res_pidx - level_first) * color_stride;
+            out_rgb[r * 3] = row[0]; out_rgb[r * 3 + 1] = row[1]; out_rgb[r * 3 + 2] = row[2];
+        }
+        if (out_alpha) out_alpha[r] = 1.0f;
+        if (out_hit) out_hit[r] = 1;
+    } else if (!found && sub == 0) {
+        out_pidx[r] = -1;
+        out_depth[r] = 0.0f;
+        if (out_rgb) { out_rgb[r * 3] = 0.0f; out_rgb[r * 3 + 1] = 0.0f; out_rgb[r * 3 + 2] = 0.0f; }
+        if (out_alpha) out_alpha[r] = 0.0f;
+        if (out_hit) out_hit[r] = 0;
+    }
+}
+
+extern "C" int wisp_spc_first_hit(const uint8_t* octree, const int16_t* points, const int32_t* exsum, const float* origins,
+                                  const float* dirs, int64_t num_rays, int level, const float* colors, int color_stride,
+                                  int32_t level_first, int32_t* pidx, float* depth, float* rgb, float* alpha, uint8_t* hit,
+                                  wisp_stream_t stream) {
+    WISP_REQUIRE(num_rays >= 0 && num_rays <= 0x7fffffffLL && level >= 0 && level <= RT_MAX_LEVEL, "bad num_rays / level");
+    WISP_REQUIRE(!colors || color_stride >= 3, "color_stride must be at least 3");
+    WISP_REQUIRE(!colors || rgb, "colors given without an rgb output");
+    WISP_REQUIRE(!rgb || colors, "an rgb output needs colors");
+    WISP_REQUIRE(level_first >= 0, "negative level_first");
+    if (num_rays == 0) return WISP_OK;
+    WISP_REQUIRE(points && exsum && origins && dirs && pidx && depth && (octree || level == 0), "null pointer");
+    hipLaunchKernelGGL(spc_first_hit_kernel, dim3((unsigned)ceil_div64(num_rays, RT8_RAYS)), dim3(RT8_RAYS * 8), 0,
+                       (hipStream_t)stream, octree, points, exsum, origins, dirs, num_rays, level, colors, color_stride,
+                       level_first, pidx, depth, rgb, alpha, hit);
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- pack boundaries
 template <typename I>
 __global__ void __launch_bounds__(256)

@@ -48,6 +48,7 @@ SIGNATURES = {
     "wisp_spc_build_bitfield": [c_vp, c_i64, c_i32, c_vp, c_vp],
     "wisp_spc_raytrace_count": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp],
     "wisp_spc_raytrace_emit": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "wisp_spc_first_hit": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_spc_trilinear_coeffs": [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp],
     "wisp_spc_trilinear_fwd": [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp],
     "wisp_spc_trilinear_bwd": [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
@@ -811,6 +812,35 @@ def spc_raytrace(octree, points, exsum, origins, dirs, level, with_exit=False):
     """kaolin.render.spc.unbatched_raytrace (octree_as.py:183-185).
     Returns (ridx i32 [M], pidx i32 [M], depth f32 [M,1|2], ray_offsets i64 [R+1])."""
     return spc_raytrace_finish(spc_raytrace_begin(octree, points, exsum, origins, dirs, level), with_exit)
+
+
+def spc_first_hit(octree, points, exsum, origins, dirs, level, colors=None, level_first=0, want_alpha=False, want_hit=False):
+    """First nugget of every ray in one launch (wisp_spc_first_hit): what spc_raytrace + mark_pack_boundaries + gathers
+    give the SPC tracer (packed_spc_tracer.py:56-90), without generating the other nuggets and without a read-back.
+    Returns (pidx i32 [R] (-1 = miss), depth f32 [R,1] (0 on a miss), rgb f32 [R,3] | None, alpha f32 [R,1] | None,
+    hit bool [R] | None).  colors: f32 [cells of `level`, >= 3], contiguous, with level_first = pyramid[1, level]."""
+    origins = _need(origins, torch.float32, "origins").reshape(-1, 3)
+    dirs = _need(dirs, torch.float32, "dirs").reshape(-1, 3)
+    octree = _need(octree, torch.uint8, "octree")
+    points = _need(points, torch.int16, "points")
+    exsum = _need(exsum, torch.int32, "exsum")
+    R, dev = origins.shape[0], origins.device
+    stride = 0
+    if colors is not None:
+        colors = _need(colors, torch.float32, "colors")
+        if colors.dim() != 2 or colors.shape[1] < 3:
+            raise ValueError(f"spc_first_hit: colors must be [cells, >= 3], got {tuple(colors.shape)}")
+        stride = colors.shape[1]
+    pidx = torch.empty(R, dtype=torch.int32, device=dev)
+    depth = torch.empty(R, 1, dtype=torch.float32, device=dev)
+    rgb = torch.empty(R, 3, dtype=torch.float32, device=dev) if colors is not None else None
+    alpha = torch.empty(R, 1, dtype=torch.float32, device=dev) if want_alpha else None
+    hit = torch.empty(R, dtype=torch.bool, device=dev) if want_hit else None
+    if R == 0:                               # (empty tensors have no address to hand over)
+        return pidx, depth, rgb, alpha, hit
+    _check(lib.wisp_spc_first_hit(_p(octree), _p(points), _p(exsum), _p(origins), _p(dirs), R, int(level), _p(colors), stride,
+                                  int(level_first), _p(pidx), _p(depth), _p(rgb), _p(alpha), _p(hit), _stream()), "spc_first_hit")
+    return pidx, depth, rgb, alpha, hit
 
 
 def spc_trilinear_coeffs(coords, voxel_points, level):

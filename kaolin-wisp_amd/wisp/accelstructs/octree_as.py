@@ -170,6 +170,15 @@ class OctreeAS(BaseAS):
         res.ray_offsets = offsets     # nugget range of every ray; used by 'uniform' raymarch
         return res
 
+    def first_hit(self, rays, level=None):
+        """The first cell of `level` every ray intersects: (pidx i32 [R], -1 where a ray hits none; depth f32 [R,1], 0 there).
+        The same numbers as the first nugget per ray of raytrace(rays, level), from one launch that stops at that nugget."""
+        if level is None:
+            level = self.max_level
+        self._to_device(rays.origins.device)
+        pidx, depth, _, _, _ = _hip().spc_first_hit(self.octree, self.points, self.prefix, rays.origins, rays.dirs, level)
+        return pidx, depth
+
     # ------------------------------------------------------------------ raymarch
     @staticmethod
     def _draw_seed():

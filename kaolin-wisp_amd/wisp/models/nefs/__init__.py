@@ -3,3 +3,4 @@ from .nerf import *
 from .neural_sdf import *
 from .image_nef import *
 from .neural_sdf_tex import *
+from .spc_field import *

@@ -88,6 +88,20 @@ def sample_surface(V: torch.Tensor, F: torch.Tensor, num_samples: int, distrib=N
     return (1 - u) * tri[:, 0] + (u * (1 - v)) * tri[:, 1] + (u * v) * tri[:, 2], normals
 
 
+def sample_surface_barycentric(V: torch.Tensor, F: torch.Tensor, num_samples: int, distrib=None):
+    """Area-weighted surface samples that carry where they came from: (points [N,3], face index i64 [N], barycentric weights
+    [N,3]), points = sum_k weights[:, k] * V[F[face, k]].  The weights are sample_surface's draw (1-sqrt(r1), sqrt(r1)(1-r2),
+    sqrt(r1) r2): non-negative, summing to 1; any per-corner attribute (texture coordinates) interpolates with them."""
+    if distrib is None:
+        distrib = area_weighted_distribution(V, F)
+    fidx = distrib.sample([num_samples])
+    u = torch.sqrt(torch.rand(num_samples, 1, dtype=V.dtype, device=V.device))
+    v = torch.rand(num_samples, 1, dtype=V.dtype, device=V.device)
+    w = torch.cat([1 - u, u * (1 - v), u * v], dim=1)
+    tri = V[F[fidx]]
+    return (w[:, :, None] * tri).sum(dim=1), fidx, w
+
+
 def sample_near_surface(V: torch.Tensor, F: torch.Tensor, num_samples: int, variance: float = 0.01, distrib=None):
     """Surface samples pushed off the surface by gaussian noise of standard deviation `variance`
     (wisp/ops/mesh/sample_near_surface.py:13-34)."""
