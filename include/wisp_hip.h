@@ -41,7 +41,7 @@ const char* wisp_last_error(void);
  * wisp_mesh_closest_tex, wisp_mesh_sample_tex, wisp_sdf_tex_train_step, wisp_sdf_query, wisp_sdf_fd_gradient, wisp_hash_sdf_query,
  * wisp_hash_sdf_fd_gradient, wisp_hash_sdf_trace_step_fused, wisp_raymarch_ray_emit_coded, wisp_nerf_mlp_operand_image_bytes,
  * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step,
- * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_composite_loss_partials, wisp_loss_sum,
+ * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_nerf_query, wisp_composite_loss_partials, wisp_loss_sum,
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
  * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
@@ -726,6 +726,24 @@ int wisp_nerf_prune_query_debug(const int16_t* dense_points, const float* unit_s
                                 const float* params, int dtype_params, int in_dim, int hidden, const float* occ_in, float decay,
                                 float min_density, float* occ_out, uint8_t* keep, float* feats, float* density,
                                 wisp_stream_t stream);
+
+/* The inference query of a radiance field (NeuralRadianceField.rgba, wisp/models/nefs/nerf.py:219-264) as ONE launch: for each of
+ * `n` sample positions the lookup of the levels below zero_from_col on the fp32 table and the exact-fp32 decoder (density
+ * network, view encoding, colour network), written as rgb [n,3] and density [n].  Bit for bit what wisp_hashgrid_interpolate_fwd
+ * followed by wisp_nerf_mlp_fwd (WISP_F32 compute) gives for the same inputs; no feature tensor exists.
+ *  coords   f32 [n, 3]
+ *  dirs     f32 view directions: [n, 3] when ridx is NULL, else the RAYS' directions [num_rays, 3] and the kernel reads
+ *           dirs[ridx[s]] (the tracer's rays.dirs.index_select(0, ridx), same bits); a ray index outside [0, num_rays) is clamped
+ *  ridx     i64 [n] or NULL (num_rays is ignored then)
+ *  table, first_idx, resolutions, codebook_bitwidth, zero_from_col (a multiple of feature_dim): as wisp_nerf_prune_query
+ *  params   f32 packed as for wisp_nerf_mlp_fwd
+ *  rgb, density: either may be NULL (not both); with rgb NULL the launch stops after layer 2 and reads no view direction
+ * This build: feature_dim 2, coord_dim 3, num_lods <= 16, hidden 64, in_dim = num_lods * 2 (<= 32), 4 view frequencies, dtype_table
+ * = dtype_params = WISP_F32; anything else returns WISP_ERR_UNSUPPORTED before any launch.  n == 0 returns WISP_OK. */
+int wisp_nerf_query(const float* coords, const float* dirs, const int64_t* ridx, int64_t num_rays, int64_t n, const void* table,
+                    int dtype_table, int feature_dim, int coord_dim, const int64_t* first_idx, const int32_t* resolutions,
+                    int num_lods, int codebook_bitwidth, int zero_from_col, const float* params, int dtype_params, int in_dim,
+                    int hidden, float* rgb, float* density, wisp_stream_t stream);
 
 /* The same decoder with the view direction given per RAY.  The reference gathers a direction per sample
  * (wisp/tracers/packed_rf_tracer.py:70-76 `rays.dirs.index_select(0, ridx)`) and positional_embedder.py:61-65 encodes each

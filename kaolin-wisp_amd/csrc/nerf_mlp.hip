@@ -29,7 +29,6 @@
 namespace {
 
 using namespace wisp_mlp;
-constexpr int K3 = 48;                    // X2 padded to the MFMA K granularity
 
 template <typename TC> struct Traits;
 template <> struct Traits<float> {
@@ -182,36 +181,18 @@ nerf_mlp_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, i
 #pragma unroll
             for (int k = 0; k < 16; ++k) x0[n * G::LDI + half * 16 + k] = Tr::from_f(live ? io_to_f<TIO>(buf[k]) : 0.0f);
         }
-        // ---- positional encoding of the view direction -> x2[:, 15..41]; zero the K padding 42..63.
-        // layout [d ; sin(2^k d) k-major ; cos(2^k d) k-major] (positional_embedder.py:61-65).  The two half-waves split the
-        // work: half 0 writes d and the sines, half 1 the cosines and the padding; one accurate sinf / cosf per band
-        // (bit-compatible with torch.sin / torch.cos to ~1 ulp).
+        // ---- positional encoding of the view direction -> x2[:, 15..41]; zero the K padding 42..63 (nerf_mlp_f32_dev.h: the
+        // fused field query expands the same encoding and the same layers 3 - 5)
+        static_assert(Geo<TC>::LDI == F32_LDI && Geo<TC>::LDH == F32_LDH && sizeof(TC) == sizeof(float), "the shared stages are the fp32 layout");
         {
             float d[3] = {0.f, 0.f, 0.f};
             if (live) { d[0] = dirs[s * 3]; d[1] = dirs[s * 3 + 1]; d[2] = dirs[s * 3 + 2]; }
-            TC* row = x2 + n * G::LDH + 15;
-            if (half == 0) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) row[a] = Tr::from_f(d[a]);
-            } else {
-#pragma unroll
-                for (int k = X2; k < 64; ++k) x2[n * G::LDH + k] = Tr::from_f(0.0f);
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int k = 0; k < NF; ++k) {
-                    const float arg = (float)(1 << k) * d[a];
-                    const float val = half == 0 ? sinf(arg) : cosf(arg);
-                    row[3 + half * 3 * NF + k * 3 + a] = Tr::from_f(val);
-                }
-            }
+            WISP_F32_VIEW_ENCODE(x2, n, half, d)
         }
         __builtin_amdgcn_wave_barrier();
 
         // ---- L1: h1 = relu(W1 x0 + b1), L2: y = W2 h1 + b2 ; density = relu(y0) ; geometry features y[1..15] -> x2[:, 0..14]
         // (nerf_mlp_f32_dev.h: the fused prune query runs the same two stages)
-        static_assert(G::LDI == F32_LDI && G::LDH == F32_LDH && sizeof(TC) == sizeof(float), "the shared stages are the fp32 layout");
         WISP_F32_LAYER1(sw, G::W1, sb, G::B1, x0, h1, n, lane)
         __builtin_amdgcn_wave_barrier();
         float y0 = 0.0f;
@@ -219,38 +200,15 @@ nerf_mlp_kernel(const TIO* __restrict__ feats, const float* __restrict__ dirs, i
         if (half == 0 && live && !BWD) out_density[s] = fmaxf(y0, 0.0f);
         __builtin_amdgcn_wave_barrier();
         // ---- L3: h2 = relu(W3 x2 + b3)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            floatx16 acc = zero16();
-            MMA<TC>::template nt<K3>(sw + G::W3 + t * 32 * G::LDH, G::LDH, x2, G::LDH, acc, lane);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = t * 32 + acc_row(r, lane);
-                h2[n * G::LDH + row] = Tr::from_f(fmaxf(acc[r] + sb[G::B3 + row], 0.0f));
-            }
-        }
+        WISP_F32_LAYER_HIDDEN(sw, G::W3, sb, G::B3, F32_K3, x2, h2, n, lane)
         __builtin_amdgcn_wave_barrier();
         // ---- L4: h3 = relu(W4 h2 + b4)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            floatx16 acc = zero16();
-            MMA<TC>::template nt<H>(sw + G::W4 + t * 32 * G::LDH, G::LDH, h2, G::LDH, acc, lane);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = t * 32 + acc_row(r, lane);
-                h3[n * G::LDH + row] = Tr::from_f(fmaxf(acc[r] + sb[G::B4 + row], 0.0f));
-            }
-        }
+        WISP_F32_LAYER_HIDDEN(sw, G::W4, sb, G::B4, H, h2, h3, n, lane)
         __builtin_amdgcn_wave_barrier();
         // ---- L5: rgb = sigmoid(W5 h3 + b5)   (rows 0..2 = regs 0..2 of the half-0 lanes)
         float sg[3] = {0.f, 0.f, 0.f};
-        {
-            floatx16 acc = zero16();
-            MMA<TC>::template nt<H>(sw + G::W5, G::LDH, h3, G::LDH, acc, lane);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) sg[c] = 1.0f / (1.0f + expf(-(acc[c] + sb[G::B5 + c])));
-            if (half == 0 && live && !BWD) { out_rgb[s * 3] = sg[0]; out_rgb[s * 3 + 1] = sg[1]; out_rgb[s * 3 + 2] = sg[2]; }
-        }
+        WISP_F32_LAYER5(sw, G::W5, sb, G::B5, h3, lane, sg)
+        if (half == 0 && live && !BWD) { out_rgb[s * 3] = sg[0]; out_rgb[s * 3 + 1] = sg[1]; out_rgb[s * 3 + 2] = sg[2]; }
         if (!BWD) { __builtin_amdgcn_wave_barrier(); continue; }
 
         // ================================= backward =================================

@@ -1,7 +1,8 @@
-// The density half of the exact-fp32 decoder - layer 1 (IN -> H, relu) and layer 2 (H -> 16) on v_mfma_f32_32x32x2_f32 - shared by
-// nerf_mlp_kernel<float, ...> (nerf_mlp.hip) and the fused prune query (prune_query.hip).  One definition of the MFMA sequence, of
-// the LDS strides and of the bias / relu epilogue, so that a density computed by either kernel from the same feature row and the
-// same parameters is the same bits.
+// The exact-fp32 decoder's stages on v_mfma_f32_32x32x2_f32 - layer 1 (IN -> H, relu), layer 2 (H -> 16), the view encoding, layers
+// 3 - 5 and the sigmoid - shared by nerf_mlp_kernel<float, ...> (nerf_mlp.hip), the fused prune query (prune_query.hip, the density
+// half) and the fused field query (nerf_query.hip, all of it).  One definition of the MFMA sequence, of the LDS strides and of the
+// bias / relu / sigmoid epilogues, so that a value computed by any of these kernels from the same feature row, the same view
+// direction and the same parameters is the same bits.
 #pragma once
 #include "wisp_common.h"
 #include "nerf_mlp_shape.h"
@@ -14,6 +15,7 @@ namespace wisp_mlp {
 constexpr int F32_PAD = 1;
 constexpr int F32_LDI = IN + F32_PAD;     // [.][IN] tiles: W1, x0
 constexpr int F32_LDH = H + F32_PAD;      // [.][H] tiles: W2 (32 rows, 16 real), h1
+constexpr int F32_K3 = 48;                // X2 = 42 colour inputs padded to the MFMA K granularity
 
 // D[i][n] += sum_k A[i][k] * B[n][k]   (A = 32 weight rows, B = the wave's 32 samples), K a multiple of 2; bit for bit an fmaf
 // chain over k = 0 .. K - 1
@@ -45,6 +47,17 @@ static __device__ __forceinline__ void f32_stage_density_params(const float* __r
     if (tid < 16) b2[tid] = packed_param(params, OB2 + tid, in_dim);
 }
 
+// the colour network the same way: W3 [H][F32_LDH] (columns X2.. zero), W4 [H][F32_LDH], W5 [32][F32_LDH] (rows 3.. zero), b3 / b4 [H],
+// b5 [32]
+static __device__ __forceinline__ void f32_stage_color_params(const float* __restrict__ params, int in_dim, float* w3, float* b3,
+                                                              float* w4, float* b4, float* w5, float* b5, int tid, int nthreads) {
+    for (int e = tid; e < H * X2; e += nthreads) w3[(e / X2) * F32_LDH + e % X2] = packed_param(params, OW3 + e, in_dim);
+    for (int e = tid; e < H * H; e += nthreads) w4[(e / H) * F32_LDH + e % H] = packed_param(params, OW4 + e, in_dim);
+    for (int e = tid; e < 3 * H; e += nthreads) w5[(e / H) * F32_LDH + e % H] = packed_param(params, OW5 + e, in_dim);
+    for (int e = tid; e < H; e += nthreads) { b3[e] = packed_param(params, OB3 + e, in_dim); b4[e] = packed_param(params, OB4 + e, in_dim); }
+    if (tid < 3) b5[tid] = packed_param(params, OB5 + tid, in_dim);
+}
+
 }  // namespace wisp_mlp
 
 // The two stages are statement macros, not functions: nerf_mlp_kernel's backward instantiations sit at the 512-register limit and
@@ -73,4 +86,46 @@ static __device__ __forceinline__ void f32_stage_density_params(const float* __r
             const float y_ = acc_[r_] + (SB)[(OB2_) + row_];                                                            \
             if (row_ == 0) Y0 = y_; else if (GEO) (X2)[(N) * wisp_mlp::F32_LDH + row_ - 1] = y_;                        \
         }                                                                                                               \
+    }
+
+// ---- the colour half: view encoding, layers 3 - 5, sigmoid - shared by nerf_mlp_kernel<float, ...> and the fused field query
+// (nerf_query.hip), statement macros for the reason given above.  HALF = LANE >> 5.
+// Positional encoding of the view direction D (float[3], zeros for a dead sample) -> X2[N][15..41], and zeros in the K padding
+// X2[N][42..63].  Layout [d ; sin(2^k d) k-major ; cos(2^k d) k-major] (positional_embedder.py:61-65).  The two half-waves split
+// the work: half 0 writes d and the sines, half 1 the cosines and the padding; one accurate sinf / cosf per band (bit-compatible
+// with torch.sin / torch.cos to ~1 ulp).  XV = the x2 tile, [32][F32_LDH]
+#define WISP_F32_VIEW_ENCODE(XV, N, HALF, D)                                                                            \
+    {                                                                                                                   \
+        float* row_ = (XV) + (N) * wisp_mlp::F32_LDH + 15;                                                              \
+        if ((HALF) == 0) {                                                                                              \
+            _Pragma("unroll") for (int a_ = 0; a_ < 3; ++a_) row_[a_] = (D)[a_];                                        \
+        } else {                                                                                                        \
+            _Pragma("unroll") for (int k_ = wisp_mlp::X2; k_ < 64; ++k_) (XV)[(N) * wisp_mlp::F32_LDH + k_] = 0.0f;     \
+        }                                                                                                               \
+        _Pragma("unroll") for (int a_ = 0; a_ < 3; ++a_) {                                                              \
+            _Pragma("unroll") for (int k_ = 0; k_ < wisp_mlp::NF; ++k_) {                                               \
+                const float arg_ = (float)(1 << k_) * (D)[a_];                                                          \
+                const float val_ = (HALF) == 0 ? sinf(arg_) : cosf(arg_);                                               \
+                row_[3 + (HALF) * 3 * wisp_mlp::NF + k_ * 3 + a_] = val_;                                               \
+            }                                                                                                           \
+        }                                                                                                               \
+    }
+// L3 (KDIM = F32_K3: X2 padded to the MFMA K granularity) and L4 (KDIM = H): HOUT[N][0..H) = relu(W XIN[N] + b); W [H][F32_LDH],
+// XIN, HOUT [32][F32_LDH]
+#define WISP_F32_LAYER_HIDDEN(SW, OW_, SB, OB_, KDIM, XIN, HOUT, N, LANE)                                               \
+    _Pragma("unroll") for (int t_ = 0; t_ < 2; ++t_) {                                                                  \
+        floatx16 acc_ = wisp_mlp::zero16();                                                                             \
+        wisp_mlp::f32_mma_nt<KDIM>((SW) + (OW_) + t_ * 32 * wisp_mlp::F32_LDH, wisp_mlp::F32_LDH, XIN, wisp_mlp::F32_LDH, \
+                                   acc_, LANE);                                                                         \
+        _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) {                                                             \
+            const int row_ = t_ * 32 + wisp_mlp::acc_row(r_, LANE);                                                     \
+            (HOUT)[(N) * wisp_mlp::F32_LDH + row_] = fmaxf(acc_[r_] + (SB)[(OB_) + row_], 0.0f);                        \
+        }                                                                                                               \
+    }
+// L5 and its epilogue: SG[c] (a float[3]) = sigmoid(W5 H3[N] + b5)[c]; rows 0..2 are registers 0..2 of the lanes below 32
+#define WISP_F32_LAYER5(SW, OW5_, SB, OB5_, H3, LANE, SG)                                                               \
+    {                                                                                                                   \
+        floatx16 acc_ = wisp_mlp::zero16();                                                                             \
+        wisp_mlp::f32_mma_nt<wisp_mlp::H>((SW) + (OW5_), wisp_mlp::F32_LDH, H3, wisp_mlp::F32_LDH, acc_, LANE);         \
+        _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_) (SG)[c_] = 1.0f / (1.0f + expf(-(acc_[c_] + (SB)[(OB5_) + c_]))); \
     }

@@ -128,6 +128,8 @@ SIGNATURES = {
                               c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp],
     "wisp_nerf_prune_query_debug": [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
                                     c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "wisp_nerf_query": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
+                        c_i32, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_dir_code": [c_vp, c_i64, c_i32, c_vp, c_vp],
     "wisp_nerf_mlp_operand_image_bytes": [c_i32],
     "wisp_nerf_mlp_build_operand_image": [c_vp, c_i32, c_i32, c_vp, c_vp],
@@ -2085,6 +2087,61 @@ def nerf_prune_query(dense_points, unit_samples, level, codebook, first_idx, res
     density = torch.empty(cells, dtype=torch.float32, device=dev)
     _check(lib.wisp_nerf_prune_query_debug(*head, _p(feats), _p(density), _stream()), "nerf_prune_query_debug")
     return occ_out if pad_rows else occ_out[:cells], (keep if pad_rows else keep[:cells].view(torch.bool)), feats, density
+
+
+def nerf_query(coords, dirs, ridx, codebook, first_idx, resolutions, codebook_bitwidth, zero_from_col, params, in_dim, hidden,
+               want_rgb=True, pad_rows=0):
+    """(rgb f32 [n, 3] or None, density f32 [n]) - lookup + exact-fp32 decoder of a radiance field in one launch (wisp_nerf_query),
+    bit for bit hashgrid_interpolate on the fp32 table followed by nerf_mlp_forward with fp32 compute.
+    dirs: the view direction of every sample [n, 3] (ridx None), or of every RAY [R, 3] with ridx int64 [n] (the kernel reads
+    dirs[ridx[s]]); may be None with want_rgb=False.
+    pad_rows (tests): the outputs are allocated with that many extra rows in front of and behind the n samples, filled with NaN that
+    the launch must leave alone, and returned WITH them."""
+    coords = _need(coords, torch.float32, "coords")
+    codebook = _need(codebook, None, "codebook")
+    first_idx = _need(first_idx, torch.int64, "codebook_first_idx")
+    params = _need(params, None, "params")
+    n = coords.shape[0]
+    if coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"coords must be [n, 3], got {tuple(coords.shape)}")
+    R = 0
+    if ridx is not None:
+        ridx = _need(ridx, torch.int64, "ridx")
+        if dirs is None or ridx.shape != (n,):
+            raise ValueError("ridx must be [n] and needs the rays' directions")
+    if dirs is not None:
+        dirs = _need(dirs, torch.float32, "dirs")
+        R = dirs.shape[0]
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or (ridx is None and R != n) or (ridx is not None and n > 0 and R < 1):
+            raise ValueError(f"dirs must be [n, 3], or [R >= 1, 3] with ridx; got {tuple(dirs.shape)} for {n} samples")
+    elif want_rgb:
+        raise ValueError("the colour needs view directions")
+    L, F = len(resolutions), codebook.shape[1]
+    first_host = _check_first_idx(first_idx, L, codebook.shape[0])
+    # every live level must own the rows its indices can reach (MultiTable's own rule: min(2^bitwidth, res^3) rows per level)
+    for l in range(min(L, -(-zero_from_col // max(F, 1)))):
+        need = min(1 << codebook_bitwidth, int(resolutions[l]) ** 3)
+        if first_host[l + 1] - first_host[l] < need:
+            raise RuntimeError(f"nerf_query: level {l} (res {resolutions[l]}) owns {first_host[l + 1] - first_host[l]} rows, "
+                               f"its indices reach {need}")
+    want = int(lib.wisp_nerf_mlp_param_count(in_dim, hidden, 4))
+    if params.numel() != want:
+        raise ValueError(f"packed decoder parameters: expected {want} floats for in_dim={in_dim}, got {params.numel()}")
+    _, res_arr, res_ptr = _host_res(resolutions)
+    dev = coords.device
+    rows = n + 2 * pad_rows
+    rgb = torch.empty(rows, 3, dtype=torch.float32, device=dev) if want_rgb else None
+    density = torch.empty(rows, dtype=torch.float32, device=dev)
+    if pad_rows:
+        density.fill_(float("nan"))
+        if rgb is not None:
+            rgb.fill_(float("nan"))
+    with _timed("nerf_query", n):
+        _check(lib.wisp_nerf_query(_p(coords), _p(dirs), _p(ridx), R, n, _p(codebook), _DTYPE_CODE.get(codebook.dtype, -1), F,
+                                   coords.shape[1], _p(first_idx), res_ptr, L, codebook_bitwidth, zero_from_col, _p(params),
+                                   _DTYPE_CODE.get(params.dtype, -1), in_dim, hidden,
+                                   _p(rgb[pad_rows:] if rgb is not None else None), _p(density[pad_rows:]), _stream()), "nerf_query")
+    return rgb, density
 
 
 def nerf_mlp_dir_code(ray_dirs, view_freqs=4):

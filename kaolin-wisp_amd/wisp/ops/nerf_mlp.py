@@ -149,6 +149,58 @@ def fused_prune_query(nef, unit_samples, debug=False, pad_rows=0):
                               nef.prune_density_decay, nef.prune_min_density, debug=debug, pad_rows=pad_rows)
 
 
+def nerf_query_supported(nef, lod_idx=None):
+    """The fused inference query (csrc/nerf_query.hip) covers this field: a CUDA 'cat' HashGrid of two-feature 3-D levels (at most
+    16) with an fp32 master table, and the fused decoder at hidden 64 with fp32 compute, outside autocast, with all ten decoder
+    tensors on the device in fp32 (an absent bias counts as zeros).  WISP_NERF_QUERY_FUSED=0 switches it off."""
+    import os
+    from wisp.models.grids import HashGrid
+    if os.environ.get("WISP_NERF_QUERY_FUSED", "1") == "0" or not getattr(nef, 'fused_decoder', False) or torch.is_autocast_enabled():
+        return False
+    grid = nef.grid
+    if not isinstance(grid, HashGrid) or grid.multiscale_type != 'cat' or grid.coord_dim != 3 or grid.feature_dim != 2 \
+            or not 1 <= grid.num_lods <= 16 or len(grid.active_lods) != grid.num_lods:
+        return False
+    if lod_idx is not None and not 0 <= lod_idx < grid.num_lods:
+        return False
+    table = grid.codebook.feats
+    if not table.is_cuda or table.dtype != torch.float32 or nef.hidden_dim != SUPPORTED["hidden"] or _compute_bf16(nef):
+        return False
+    from types import SimpleNamespace
+    if not supports(nef, SimpleNamespace(is_cuda=True, shape=(0, nef.effective_feature_dim()), dtype=torch.float32)):
+        return False                                       # (what the lookup would hand the decoder: fp32 rows on the table's device)
+    return not any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in _decoder_tensors(nef))
+
+
+def fused_nerf_query(nef, coords, ray_d=None, ray_dirs=None, ridx=None, lod_idx=None, want_rgb=True, pad_rows=0):
+    """(rgb [n,3] fp32 or None, density [n,1] fp32) of NeuralRadianceField.rgba for a field nerf_query_supported() accepts, in one
+    launch and without a feature tensor; the same bits as grid.interpolate + fused_nerf_decoder.  The view direction comes per
+    sample (ray_d [n,3]) or per ray (ray_dirs [R,3] with ridx int64 [n]: ray_dirs.index_select(0, ridx) is never built).
+    Inference only: inputs that require a gradient are refused."""
+    tensors = [coords, ray_d, ray_dirs] + [nef.grid.codebook.feats] + _decoder_tensors(nef)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError("fused_nerf_query has no backward: call it under torch.no_grad(), or take the modular path")
+    if (ray_d is None) == (ray_dirs is None) and want_rgb:
+        raise ValueError("give the view direction either per sample (ray_d) or per ray (ray_dirs + ridx)")
+    if (ray_dirs is None) != (ridx is None):
+        raise ValueError("ray_dirs and ridx go together")
+    C = _hip()
+    grid = nef.grid
+    cb = grid.codebook
+    params = _decoder_tensors(nef)
+    H, I = nef.hidden_dim, nef.effective_feature_dim()
+    shapes = ((H, I), (H,), (16, H), (16,), (H, 42), (H,), (H, H), (H,), (3, H), (3,))
+    flat = _flat_view([p.detach() if p is not None else None for p in params])
+    packed = flat if flat is not None else _pack(params, shapes)
+    if lod_idx is None:
+        lod_idx = len(grid.active_lods) - 1               # what NeuralRadianceField.rgba queries; 'cat' zeroes the columns from there on
+    res = [int(r) for r in cb.resolutions.reshape(-1).tolist()]
+    rgb, density = C.nerf_query(coords.detach(), (ray_d if ray_d is not None else ray_dirs), ridx, cb.feats.detach(), cb.begin_idxes,
+                                res, grid.codebook_bitwidth, lod_idx * grid.feature_dim, packed, I, H, want_rgb=want_rgb,
+                                pad_rows=pad_rows)
+    return rgb, density.reshape(-1, 1)
+
+
 def fused_nerf_decoder(nef, feats, ray_d):
     """(rgb [S,3] fp32, density [S,1] fp32) for the decoder shapes of the reference's app/nerf configs (see SUPPORTED)."""
     compute_bf16 = _compute_bf16(nef)

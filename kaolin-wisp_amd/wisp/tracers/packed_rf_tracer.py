@@ -53,6 +53,15 @@ class PackedRFTracer(BaseTracer):
     def get_required_nef_channels(self):
         return {"rgb", "density"}
 
+    def _fused_query(self, nef, lod_idx, extra_channels):
+        """True when this call takes the one-launch field query: the plain attribute `fused_query` is set (absent = off; not a
+        constructor argument, the schema is the reference's), gradients are disabled, no extra channel is asked for and the field
+        is one wisp.ops.nerf_mlp.nerf_query_supported accepts."""
+        if not getattr(self, 'fused_query', False) or torch.is_grad_enabled() or extra_channels:
+            return False
+        from wisp.ops.nerf_mlp import nerf_query_supported
+        return nerf_query_supported(nef, lod_idx)
+
     def trace(self, nef, rays, channels, extra_channels,
               lod_idx=None, raymarch_type='voxel', num_steps=64, step_size=1.0, bg_color='white', jitter=None):
         """Raymarch -> field query -> fused compositing.  Returns RenderBuffer(depth, hit, rgb, alpha, extras)."""
@@ -67,7 +76,15 @@ class PackedRFTracer(BaseTracer):
         num_samples = samples.shape[0]
         self.prev_num_samples = num_samples
 
-        hit_ray_d = rays.dirs.index_select(0, ridx)
+        if self._fused_query(nef, lod_idx, extra_channels):
+            # inference on the shipped NeRF shape: lookup + decoder as ONE launch that reads every sample's direction through its
+            # ray index (csrc/nerf_query.hip) - no per-sample direction tensor, no feature tensor; same bits as the calls below
+            from wisp.ops.nerf_mlp import fused_nerf_query
+            hit_ray_d = None
+            color, density = fused_nerf_query(nef, samples, ray_dirs=rays.dirs, ridx=ridx, lod_idx=lod_idx)
+        else:
+            hit_ray_d = rays.dirs.index_select(0, ridx)
+            color = None
         if self.bg_color.device != rays.origins.device:
             self.bg_color = self.bg_color.to(rays.origins.device)
         bg = self._bg_host()
@@ -75,13 +92,14 @@ class PackedRFTracer(BaseTracer):
         ray_offsets = getattr(rm, "ray_offsets", None)
         # (samples / directions that require a gradient - pose or camera optimisation - stay on the modular path: its
         #  HashGridInterpolate.backward returns the reference's grad_coords, the one-node trace differentiates table + decoder only)
-        coords_need_grad = samples.requires_grad or hit_ray_d.requires_grad
-        if ray_offsets is not None and not coords_need_grad and _fused.supports(nef, lod_idx, extra_channels):
+        coords_need_grad = samples.requires_grad or (hit_ray_d is not None and hit_ray_d.requires_grad)
+        if color is None and ray_offsets is not None and not coords_need_grad and _fused.supports(nef, lod_idx, extra_channels):
             # the shipped NeRF shape: lookup, decoder and compositing as ONE autograd node (same kernels, same numbers)
             rgb, alpha, depth, hit = _fused.fused_trace(nef, samples, hit_ray_d, deltas, depths if want_depth else None, ray_offsets, N,
                                                         bg, lod_idx)
             return RenderBuffer(depth=depth, hit=hit, rgb=rgb, alpha=alpha)
-        color, density = nef(coords=samples, ray_d=hit_ray_d, lod_idx=lod_idx, channels=["rgb", "density"])
+        if color is None:
+            color, density = nef(coords=samples, ray_d=hit_ray_d, lod_idx=lod_idx, channels=["rgb", "density"])
         density = density.reshape(num_samples, 1)
         if ray_offsets is not None and not extra_channels:
             # every ray is its own (possibly empty) pack: no boundary compaction, no host read of the pack count

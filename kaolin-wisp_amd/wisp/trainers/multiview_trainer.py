@@ -944,6 +944,10 @@ class MultiviewTrainStep:
         return loss.detach(), self.pipeline.tracer.get_prev_num_samples()
 
 
+# What MultiviewTrainer.evaluate_metrics sets the tracer's `fused_query` to for its own renders (None: leaves the tracer alone).
+EVAL_FUSED_QUERY = True
+
+
 @dataclass
 class ConfigMultiviewTrainer(ConfigBaseTrainer):
     """Field names and defaults of wisp/trainers/multiview_trainer.py:33-63 (the YAML schema under `trainer:`)."""
@@ -1057,10 +1061,77 @@ class MultiviewTrainer(BaseTrainer):
         log.info('EPOCH {}/{} | total loss: {:>.3E} | rgb loss: {:>.3E}'.format(
             self.epoch, self.max_epochs, m.average_metric('total_loss'), m.average_metric('rgb_loss')))
 
+    def evaluate_metrics(self, validation_dataset, lod_idx, name=None):
+        """Per-view metrics over the validation set (multiview_trainer.py:191-255): every view is rendered at full resolution
+        through the tracker's visualizer (wisp.trainers.validation.render when the tracker has none), compared with its image
+        through wisp.ops.image.psnr, and - with cfg.save_valid_imgs - written as val/{idx}-{name}.png under the tracker's log
+        directory (the bytes of rb.image().byte().rgb).  The mean of each metric is logged in the reference's format, the best
+        value so far is kept in return_dict, and the dict of means is returned.  'ssim' and 'lpips' need packages this project
+        does not depend on; EXR needs pyexr and is skipped with the reference's one-time log line.
+        The renders run in fp32 (as validate() does) with the tracer's fused_query on: lookup + decoder in one launch where the
+        field allows it, the same bits as the modular path; the attribute is put back afterwards."""
+        from wisp.core import RenderBuffer
+        from wisp.ops.image import psnr, write_png
+        from wisp.trainers import validation
+        for metric in ('ssim', 'lpips'):
+            if metric in self.cfg.valid_metrics:
+                raise NotImplementedError(f"valid_metrics: {metric!r} needs a package this project does not depend on "
+                                          f"({'scikit-image' if metric == 'ssim' else 'lpips'}); only 'psnr' is provided")
+        valid_log_dir = os.path.join(self.tracker.log_dir, "val")
+        img_shape = validation_dataset.img_shape
+        data = validation_dataset.data
+        all_rays = data["rays"]
+        imgs = [img.to(self.device) for img in data["rgb"]]
+        ray_os = list(all_rays.origins.to(self.device))
+        ray_ds = list(all_rays.dirs.to(self.device))
+        metrics_dict = {key: 0.0 for key in self.cfg.valid_metrics}
+        visualizer = getattr(self.tracker, 'visualizer', None)
+        if self.cfg.save_valid_imgs:
+            os.makedirs(valid_log_dir, exist_ok=True)
+        with validation._fused_query_as(self.pipeline.tracer, EVAL_FUSED_QUERY), torch.no_grad():
+            for idx, (img, ray_o, ray_d) in enumerate(zip(imgs, ray_os, ray_ds)):
+                rays = Rays(ray_o, ray_d, dist_min=all_rays.dist_min, dist_max=all_rays.dist_max).reshape(-1, 3)
+                if visualizer is not None:
+                    rb = visualizer.render(self.pipeline, rays, lod_idx=lod_idx)
+                else:
+                    rb = validation.render(self.pipeline, rays, lod_idx=lod_idx)
+                rb = rb.reshape(*img_shape[:2], -1)
+                gts = img.reshape(*img_shape[:2], -1)
+                if 'psnr' in self.cfg.valid_metrics:
+                    metrics_dict['psnr'] += psnr(rb.rgb[..., :3], gts[..., :3])
+                out_name = f"{idx}"
+                if name is not None:
+                    out_name += "-" + name
+                if self.cfg.save_valid_imgs:
+                    if not hasattr(self, "exr_exception"):
+                        self.exr_exception = True
+                        log.info("Skipping EXR logging since pyexr is not found.")
+                    write_png(os.path.join(valid_log_dir, out_name + ".png"), rb.cpu().image().byte().rgb.numpy())
+        log_text = 'EPOCH {}/{}'.format(self.epoch, self.max_epochs)
+        for key in metrics_dict:
+            metrics_dict[key] /= len(imgs)
+            if key not in self.return_dict:
+                self.return_dict[key] = metrics_dict[key]
+            else:
+                self.return_dict[key] = max(self.return_dict[key], metrics_dict[key])
+            if key == 'psnr':
+                log_text += ' | {}: {:.2f}'.format(f"{name} {key}", metrics_dict[key])
+            else:
+                log_text += ' | {}: {:.6f}'.format(f"{name} {key}", metrics_dict[key])
+        log.info(log_text)
+        return metrics_dict
+
     def validate(self):
-        """PSNR over the validation views (multiview_trainer.py:257-303 without image / table writers)."""
+        """PSNR over the validation views (multiview_trainer.py:257-303 without the table writers).  With cfg.save_valid_imgs the
+        views also go to val/*.png, through evaluate_metrics."""
         if self.validation_dataset is None:
             return None
+        if self.cfg.save_valid_imgs:
+            self.pipeline.eval()
+            lod_idx = self.pipeline.nef.grid.num_lods - 1
+            self.evaluate_metrics(self.validation_dataset, lod_idx, name=f"lod{lod_idx}")
+            self.pipeline.train()
+            return self.return_dict
         from wisp.trainers.validation import evaluate_psnr
         data = self.validation_dataset.data
         rays, rgb = data["rays"], data["rgb"]

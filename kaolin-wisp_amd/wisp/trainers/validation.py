@@ -26,12 +26,37 @@ def assert_master_current(module):
                 fn(m, "", False)
 
 
-def render(pipeline, rays: Rays, lod_idx=None, render_batch=10000, channels=None, amp=False):
-    """Full-resolution inference in chunks of `render_batch` rays; RenderBuffer channels concatenated along dim 0."""
+class _fused_query_as:
+    """`tracer.fused_query` set to `value` for the length of a with-block (None: left alone) and put back afterwards - to the
+    value it had, or removed if it was absent - whatever the block raises."""
+    _ABSENT = object()
+
+    def __init__(self, tracer, value):
+        self.tracer, self.value = tracer, value
+
+    def __enter__(self):
+        if self.value is not None:
+            self.before = getattr(self.tracer, 'fused_query', self._ABSENT)
+            self.tracer.fused_query = bool(self.value)
+        return self
+
+    def __exit__(self, *exc):
+        if self.value is not None:
+            if self.before is self._ABSENT:
+                del self.tracer.fused_query
+            else:
+                self.tracer.fused_query = self.before
+        return False
+
+
+def render(pipeline, rays: Rays, lod_idx=None, render_batch=10000, channels=None, amp=False, fused_query=None):
+    """Full-resolution inference in chunks of `render_batch` rays; RenderBuffer channels concatenated along dim 0.
+    fused_query: None leaves the tracer as it is; True / False sets its `fused_query` attribute (PackedRFTracer: lookup + decoder
+    as one launch, the same bits) for this call and restores it."""
     if not amp:
         assert_master_current(pipeline)               # fp32 inference reads the master weights, not the shadow
     kw = {} if channels is None else {"channels": channels}
-    with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=amp):
+    with _fused_query_as(pipeline.tracer, fused_query), torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=amp):
         if render_batch > 0:
             rb = RenderBuffer()
             for pack in rays.split(render_batch):

@@ -1,0 +1,115 @@
+"""Inference on the nerf_hash.yaml field, fused query against modular ops: one JSON line, also written to --out
+(default profiles/bench_nerf_eval.json).
+
+Two comparisons, each the one-launch query of csrc/nerf_query.hip against the modular path (WISP_NERF_QUERY_FUSED=0: the hash-grid
+lookup launch into a feature tensor, then the exact-fp32 decoder launch) in ONE process, repetitions alternating, medians of wall
+time around a device synchronisation:
+  query   lookup + decoder alone at 2^18 and 2^21 random sample positions with per-sample view directions
+  view    a whole 800 x 800 view through wisp.trainers.validation.render at render_batch 10 000 and 2^17 (march, the
+          index_select of the ray directions, query, compositing)
+The field is the untrained nerf_hash.yaml pipeline with tables drawn at std 0.1 and a dense level-7 octree: the cost of the query
+does not depend on what the field has learned, and every ray that meets the cube carries samples."""
+import argparse
+import json
+import logging
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd"), os.path.join(ROOT, "scripts")]
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def compare(fns, reps):
+    """fns: dict mode -> callable; alternating repetitions after one warm-up of each -> medians, minima and the spread (max - min)"""
+    times = {m: [] for m in fns}
+    for rep in range(reps + 1):
+        for mode, fn in fns.items():
+            ms = timed(fn)
+            if rep:
+                times[mode].append(ms)
+    out = {}
+    for m, v in times.items():
+        out[f"{m}_ms_median"] = round(statistics.median(v), 4)
+        out[f"{m}_ms_min"] = round(min(v), 4)
+        out[f"{m}_ms_spread"] = round(max(v) - min(v), 4)
+    out["speedup_median"] = round(out["modular_ms_median"] / out["fused_ms_median"], 3)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--res", type=int, default=800)
+    ap.add_argument("--num-steps", type=int, default=512)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_nerf_eval.json"))
+    args = ap.parse_args(argv)
+    logging.basicConfig(level=logging.WARNING)
+    from render_nerf import orbit_cameras
+    from train_nerf_synthetic import build_pipeline
+    from wisp.ops.nerf_mlp import fused_nerf_query, nerf_query_supported
+    from wisp.ops.raygen import generate_centered_pixel_coords, generate_pinhole_rays
+    from wisp.trainers.validation import render
+    dev = "cuda:0"
+    torch.manual_seed(0)
+    pipeline = build_pipeline(dev, args.num_steps)
+    nef = pipeline.nef
+    with torch.no_grad():
+        nef.grid.codebook.feats.normal_(0.0, 0.1)
+    pipeline.eval()
+    os.environ["WISP_NERF_QUERY_FUSED"] = "1"
+    with torch.no_grad():
+        assert nerf_query_supported(nef)
+    rec = dict(bench="nerf_eval", device=torch.cuda.get_device_name(0), reps=args.reps, num_steps=args.num_steps, query={}, view={})
+    for log2n in (18, 21):
+        n = 1 << log2n
+        g = torch.Generator(device=dev).manual_seed(log2n)
+        coords = torch.rand(n, 3, device=dev, generator=g) * 2.0 - 1.0
+        dirs = torch.nn.functional.normalize(torch.randn(n, 3, device=dev, generator=g), dim=1)
+
+        def fused():
+            with torch.no_grad():
+                fused_nerf_query(nef, coords, ray_d=dirs)
+
+        def modular():
+            with torch.no_grad():
+                nef(coords=coords, ray_d=dirs, channels=["rgb", "density"])
+        with torch.no_grad():
+            a = fused_nerf_query(nef, coords, ray_d=dirs)
+            b = nef(coords=coords, ray_d=dirs, channels=["rgb", "density"])
+        row = compare(dict(fused=fused, modular=modular), args.reps)
+        row["equal_bits"] = bool(torch.equal(a[0], b[0]) and torch.equal(a[1].reshape(-1), b[1].reshape(-1)))
+        rec["query"][f"2^{log2n}"] = row
+    cam = orbit_cameras(1, args.res, args.res)[0]
+    rays = generate_pinhole_rays(cam, generate_centered_pixel_coords(args.res, args.res, device=dev)).reshape(-1, 3)
+    for batch in (10000, 1 << 17):
+        out = {}
+
+        def view(flag, key):
+            torch.manual_seed(1)                                    # (the march's jitter seeds follow torch's CPU generator)
+            out[key] = render(pipeline, rays, render_batch=batch, channels=["rgb"], fused_query=flag).rgb
+        row = compare(dict(fused=lambda: view(True, "f"), modular=lambda: view(False, "m")), args.reps)
+        row["equal_bits"] = bool(torch.equal(out["f"], out["m"]))
+        rec["view"][f"render_batch_{batch}"] = dict(res=args.res, **row)
+    line = json.dumps(rec)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+    return rec
+
+
+if __name__ == "__main__":
+    main()

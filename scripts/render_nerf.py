@@ -1,0 +1,137 @@
+"""Render a trained radiance field to pictures: an orbit of look-at cameras on the training hemisphere, one rgb / depth / alpha PNG
+per view, one JSON line with the timing.
+
+    python scripts/render_nerf.py --checkpoint PATH [--views 8] [--res 800 800] [--render-batch 10000] --out DIR [--no-fused]
+    python scripts/render_nerf.py --write-synlego DIR --steps K [...] --out DIR
+
+--checkpoint PATH is a file written by wisp.trainers.validation.save_pipeline: a 'full' checkpoint is the pipeline itself, a
+state_dict checkpoint is loaded into the nerf_hash.yaml pipeline of scripts/train_nerf_synthetic.py.  With --write-synlego DIR a
+SynLego scene is written to DIR and fitted for K iterations first (the flow of train_nerf_synthetic.py), so the script runs where
+neither a dataset nor a checkpoint exists.
+
+The views are traced through wisp.trainers.validation.render with the tracer's `fused_query` on - lookup + decoder of every chunk
+in one launch (csrc/nerf_query.hip), the same bits as the modular ops - unless --no-fused is given or the field is not one the
+kernel covers (the JSON line reports which)."""
+import argparse
+import json
+import logging
+import math
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd"), os.path.join(ROOT, "scripts")]
+
+
+def orbit_cameras(views, width, height, elevation_cos=0.5):
+    """`views` LookAtCameras evenly spaced on the circle of the training hemisphere (synlego.cameras: radius CAMERA_RADIUS, y up)
+    whose polar angle from +y has the cosine `elevation_cos`, looking at the origin with the training field of view."""
+    import synlego
+    from wisp.ops.raygen import LookAtCamera
+    sin_phi = math.sqrt(1.0 - elevation_cos ** 2)
+    cams = []
+    for k in range(views):
+        theta = 2.0 * math.pi * k / max(views, 1)
+        eye = [synlego.CAMERA_RADIUS * sin_phi * math.cos(theta), synlego.CAMERA_RADIUS * elevation_cos,
+               synlego.CAMERA_RADIUS * sin_phi * math.sin(theta)]
+        cams.append(LookAtCamera(eye=eye, at=[0.0, 0.0, 0.0], up=[0.0, 1.0, 0.0], fov=synlego.CAMERA_ANGLE_X, width=width,
+                                 height=height, near=synlego.NEAR, far=synlego.FAR))
+    return cams
+
+
+def fit_synlego(root, steps, dev, views=8, res=64, num_steps=512, num_samples=1024):
+    """write a small SynLego scene to `root` and fit the nerf_hash.yaml pipeline to it for `steps` iterations"""
+    from train_nerf_synthetic import build_pipeline, write_synlego_scene
+    from wisp.datasets import SampleRays, load_multiview_dataset
+    from wisp.trainers import ConfigAdamW, ConfigMultiviewTrainer, MultiviewTrainer
+    write_synlego_scene(root, views=(views, 1, 1), res=res, device=dev)
+    train = load_multiview_dataset(root, split='train', transform=SampleRays(num_samples), bg_color=(0.0, 0.0, 0.0), mip=0,
+                                   dataset_num_workers=-1)
+    torch.manual_seed(0)
+    pipeline = build_pipeline(dev, num_steps, (0.0, 0.0, 0.0))
+    epochs = max(1, -(-(steps + 1) // len(train)))                      # (the first iteration only sizes the batch)
+    cfg = ConfigMultiviewTrainer(optimizer=ConfigAdamW(lr=1e-3, eps=1e-16, weight_decay=1e-6), grid_lr_weight=500.0, enable_amp=True,
+                                 prune_every=100, rgb_loss_type='huber', rgb_loss_denom='rays', max_epochs=epochs, scheduler=True,
+                                 valid_every=-1, save_every=-1, profile_nvtx=False)
+    trainer = MultiviewTrainer(cfg, pipeline, train, device=dev)
+    trainer.is_optimization_running = True
+    while trainer.is_optimization_running and trainer.total_iterations <= steps:
+        trainer.iterate()
+    return pipeline
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--checkpoint", metavar="PATH", default=None, help="a file written by save_pipeline")
+    ap.add_argument("--write-synlego", metavar="DIR", default=None, help="write a SynLego scene to DIR and fit it first")
+    ap.add_argument("--steps", type=int, default=200, help="--write-synlego: training iterations")
+    ap.add_argument("--train-views", type=int, default=8, help="--write-synlego: training views")
+    ap.add_argument("--train-res", type=int, default=64, help="--write-synlego: side of the training images in pixels")
+    ap.add_argument("--num-steps", type=int, default=512, help="raymarch steps of the pipeline this script builds")
+    ap.add_argument("--views", type=int, default=8, help="frames to render")
+    ap.add_argument("--res", type=int, nargs=2, default=(800, 800), metavar=("H", "W"))
+    ap.add_argument("--render-batch", type=int, default=10000, help="rays per chunk")
+    ap.add_argument("--out", metavar="DIR", required=True)
+    ap.add_argument("--no-fused", action="store_true", help="leave the tracer's fused_query off (the modular ops)")
+    args = ap.parse_args(argv)
+    if (args.checkpoint is None) == (args.write_synlego is None):
+        ap.error("give exactly one of --checkpoint PATH and --write-synlego DIR")
+    logging.basicConfig(level=logging.WARNING, format="%(message)s")
+    assert torch.cuda.is_available(), "render_nerf.py renders on the GPU"
+    dev = "cuda:0"
+    from wisp.core import RenderBuffer
+    from wisp.ops.image import write_png
+    from wisp.ops.nerf_mlp import nerf_query_supported
+    from wisp.ops.raygen import generate_centered_pixel_coords, generate_pinhole_rays
+    from wisp.trainers.validation import load_pipeline, render
+    if args.checkpoint is not None:
+        from collections.abc import Mapping
+        obj = torch.load(args.checkpoint, map_location=dev, weights_only=False)
+        if isinstance(obj, Mapping):
+            from train_nerf_synthetic import build_pipeline
+            pipeline = load_pipeline(args.checkpoint, build_pipeline(dev, args.num_steps), map_location=dev)
+        else:
+            pipeline = obj
+        pipeline = pipeline.to(dev)
+    else:
+        pipeline = fit_synlego(args.write_synlego, args.steps, dev, views=args.train_views, res=args.train_res, num_steps=args.num_steps)
+    pipeline.eval()
+    h, w = args.res
+    fused = not args.no_fused
+    os.makedirs(args.out, exist_ok=True)
+    times, samples = [], []
+    for k, cam in enumerate(orbit_cameras(args.views, w, h)):
+        grid = generate_centered_pixel_coords(w, h, device=dev)
+        rays = generate_pinhole_rays(cam, grid).reshape(-1, 3)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        count = 0
+        rb = RenderBuffer()
+        for pack in (rays.split(args.render_batch) if args.render_batch > 0 else [rays]):
+            rb += render(pipeline, pack, render_batch=-1, channels=["rgb", "depth", "alpha"], fused_query=fused)
+            count += pipeline.tracer.get_prev_num_samples()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+        samples.append(count)
+        img = rb.reshape(h, w, -1).cpu().image().byte()
+        write_png(os.path.join(args.out, f"rgb_{k:03d}.png"), img.rgb.numpy())
+        write_png(os.path.join(args.out, f"depth_{k:03d}.png"), img.depth.numpy())
+        write_png(os.path.join(args.out, f"alpha_{k:03d}.png"), img.alpha.numpy())
+    grid_ = pipeline.nef.grid
+    with torch.no_grad():
+        took_fused = bool(fused and nerf_query_supported(pipeline.nef))
+    print(json.dumps(dict(metric="render_nerf", frames=len(times), res=[h, w], render_batch=args.render_batch,
+                          ms_per_frame=round(sum(times) / max(len(times), 1), 3),
+                          samples_per_frame=int(sum(samples) / max(len(samples), 1)), fused_query=took_fused,
+                          field=dict(grid=type(grid_).__name__, num_lods=int(getattr(grid_, "num_lods", 0)),
+                                     feature_dim=int(getattr(grid_, "feature_dim", 0)),
+                                     codebook_bitwidth=int(getattr(grid_, "codebook_bitwidth", 0)),
+                                     multiscale_type=getattr(grid_, "multiscale_type", None),
+                                     hidden_dim=int(pipeline.nef.hidden_dim)))))
+
+
+if __name__ == "__main__":
+    main()
