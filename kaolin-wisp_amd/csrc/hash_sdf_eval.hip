@@ -6,6 +6,7 @@
 // hash_sdf_eval_dev.h.
 #include "wisp_common.h"
 #include "hash_sdf_eval_dev.h"
+#include "sphere_trace_dev.h"
 
 #define HSDF_BLOCK 256
 #define HSDF_GROUPS (HSDF_BLOCK / HSDF_GROUP)
@@ -72,76 +73,30 @@ hash_sdf_point_gradient_kernel(const float* __restrict__ coords, int64_t n, Hash
 
 // One marching iteration of PackedSDFTracer.trace (wisp/tracers/packed_sdf_tracer.py:118-146) including the field query
 // nef(coords=x, channels="sdf") of a NeuralSDF over a HashGrid.  16 lanes own one pack: all 16 run the (pack-uniform)
-// bookkeeping of sphere_trace_step_kernel (csrc/render.hip: the same statements in the same order under the same contraction
-// setting, as sdf_trace_fused_kernel of csrc/spc_interp.hip restates them), lane 0 stores the state, and the packs still
-// marching evaluate the field at the new position.  A group leaves as a whole, so nothing below the exits is wave-wide.
+// bookkeeping of sphere_trace_step (sphere_trace_dev.h), lane 0 stores the state, and the packs still marching evaluate the
+// field at the new position.  A group leaves as a whole, so nothing below the exits is wave-wide.
 template <typename T>
 __global__ void __launch_bounds__(HSDF_BLOCK)
-hash_sdf_march_kernel(int64_t num_packs, int first, const float* __restrict__ nug_o, const float* __restrict__ nug_d,
-                            const float* __restrict__ nug_depth, const int32_t* __restrict__ nug_pidx, float dist_max,
-                            float thr_close, float thr_avg, float* __restrict__ t, float* __restrict__ dist,
-                            float* __restrict__ dist_prev, uint8_t* __restrict__ mask, uint8_t* __restrict__ hit,
-                            const int32_t* __restrict__ curr_in, int32_t* __restrict__ curr_out, int64_t* __restrict__ curr_pidx,
-                            float* __restrict__ x, HashSdfField fld, float scale, int32_t* __restrict__ any_active) {
+hash_sdf_march_kernel(SphereTraceState st, int first, HashSdfField fld, float scale, int32_t* __restrict__ any_active) {
     extern __shared__ float s_hsdf[];
     const HashSdfLds s = hash_sdf_stage(s_hsdf, fld);
     const int c = threadIdx.x & (HSDF_GROUP - 1), grp = threadIdx.x / HSDF_GROUP;
     const int64_t p = (int64_t)blockIdx.x * HSDF_GROUPS + grp;
-    if (p >= num_packs) return;
+    if (p >= st.num_packs) return;
     float px, py, pz;
     bool m;
     if (first) {
-        m = mask[p] != 0;
-        px = x[p * 3]; py = x[p * 3 + 1]; pz = x[p * 3 + 2];
+        m = st.mask[p] != 0;
+        px = st.x[p * 3]; py = st.x[p * 3 + 1]; pz = st.x[p * 3 + 2];
     } else {
-#pragma clang fp contract(off)
-        const int32_t cur = curr_in[p];
-        m = mask[p] != 0;
-        const bool was = m;
-        bool h = hit[p] != 0;
-        const float dd = dist[p];
-        float tt = t[p] + dd;                                                        // t += dist          (:120)
-        if (m) {
-            h = fabsf(dd) < thr_close;                                               // :122
-            h = h || (fabsf(dd + dist_prev[p]) * 0.5f < thr_avg);                    // :123-124
-            m = tt < dist_max;                                                       // :125
-        }
-        m = m && !h;                                                                 // :126
-        const float dprev = dd;
-        int32_t nxt = -1;
-        if (cur > -1) {                                                              // find_depth_bound (:131)
-            uint32_t i = (uint32_t)cur;
-            const uint32_t stop = (p == num_packs - 1) ? (uint32_t)num_packs : (uint32_t)curr_in[p + 1];
-            while (i < stop) {
-                const float entry = nug_depth[2 * (int64_t)i], exit_ = nug_depth[2 * (int64_t)i + 1];
-                if ((tt >= entry && tt <= exit_) || tt < entry) { nxt = (int32_t)i; break; }
-                ++i;
-            }
-        }
-        const bool keep_prev = m;                                                    // :129 runs before :132
-        m = m && (nxt != -1);                                                        // :132
-        const bool jumped = nxt != cur;                                              // :133
-        const int32_t now = m ? nxt : cur;                                           // :134
-        if (m && jumped) tt = nug_depth[2 * (int64_t)now];                           // :136
-        px = nug_o[p * 3 + 0] + nug_d[p * 3 + 0] * tt;                               // :137-139 / :121
-        py = nug_o[p * 3 + 1] + nug_d[p * 3 + 1] * tt;
-        pz = nug_o[p * 3 + 2] + nug_d[p * 3 + 2] * tt;
-        if (c == 0) {
-            if (keep_prev) dist_prev[p] = dprev;
-            if (m || was) { x[p * 3 + 0] = px; x[p * 3 + 1] = py; x[p * 3 + 2] = pz; }
-            if (m) curr_pidx[p] = (int64_t)nug_pidx[now];
-            t[p] = tt;
-            mask[p] = m ? 1 : 0;
-            hit[p] = h ? 1 : 0;
-            curr_out[p] = now;
-        }
+        m = sphere_trace_step(st, p, c == 0, px, py, pz);
     }
     if (!m) return;
     if (c == 0 && any_active) atomicAdd(any_active, 1);
     const float o = hash_sdf_eval_point<T>(fld, s, s.in + grp * s.stride, c, px, py, pz);
     if (c == 0) {
 #pragma clang fp contract(off)
-        dist[p] = o * scale;
+        st.dist[p] = o * scale;
     }
 }
 
@@ -221,15 +176,14 @@ extern "C" int wisp_hash_sdf_trace_step_fused(int64_t num_packs, int first, cons
     if (const int rc = hash_sdf_fill(fld, __func__, codebook, feats_dtype, begin_idxes, resolutions, num_lods, feature_dim,
                                      codebook_bitwidth, multiscale, zero_from_col, w1, b1, w2, b2, hidden)) return rc;
     if (num_packs == 0) return WISP_OK;
-    WISP_REQUIRE(nug_o && nug_d && nug_depth && nug_pidx && t && dist && dist_prev && mask && hit && curr_in && curr_out &&
-                 curr_pidx && x, "null pointer");
+    const SphereTraceState st{num_packs, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev,
+                              mask, hit, curr_in, curr_out, curr_pidx, x};
+    WISP_REQUIRE(sphere_trace_state_complete(st), "null pointer");
     const size_t lds = hash_sdf_lds(fld);
     WISP_REQUIRE(lds <= 64 * 1024, "LDS budget exceeded");
     const dim3 grid((unsigned)ceil_div64(num_packs, HSDF_GROUPS)), block(HSDF_BLOCK);
     hipStream_t s = (hipStream_t)stream;
-#define HSDF_T(T) hipLaunchKernelGGL((hash_sdf_march_kernel<T>), grid, block, lds, s, num_packs, first, nug_o, nug_d, nug_depth,   \
-                                     nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit, curr_in, curr_out,         \
-                                     curr_pidx, x, fld, scale, any_active)
+#define HSDF_T(T) hipLaunchKernelGGL((hash_sdf_march_kernel<T>), grid, block, lds, s, st, first, fld, scale, any_active)
     HSDF_DISPATCH(HSDF_T);
 #undef HSDF_T
     WISP_CHECK_LAUNCH();

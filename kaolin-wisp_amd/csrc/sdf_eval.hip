@@ -1,9 +1,12 @@
-// Evaluation of an nglod field outside training and marching, for gfx950: the signed distance (or NeuralSDFTex's four raw
-// outputs) at arbitrary points, the intersection-over-union counters of a validation batch, and central-difference normals -
-// one launch each.  The modular path is an octree query, a multi-level trilinear launch and two library GEMMs per call, six
-// times over for a normal, and one host read-back per 512-point validation batch.  Field evaluation: sdf_eval_dev.h.
+// Evaluation of an nglod field outside training, for gfx950: the signed distance (or NeuralSDFTex's four raw outputs) at
+// arbitrary points, the intersection-over-union counters of a validation batch, central-difference normals, and one marching
+// iteration of PackedSDFTracer including the field query - one launch each.  The modular path is an octree query, a multi-level
+// trilinear launch and two library GEMMs per call - six times over for a normal, once more with ~25 masked tensor ops, a
+// scatter and a `mask.any()` read-back per marching iteration - and one host read-back per 512-point validation batch.
+// Field evaluation: sdf_eval_dev.h.  Marching bookkeeping: sphere_trace_dev.h.
 #include "wisp_common.h"
 #include "sdf_eval_dev.h"
+#include "sphere_trace_dev.h"
 
 #define SDFE_BLOCK 256
 #define SDFE_GROUPS (SDFE_BLOCK / SDFE_GROUP)
@@ -71,6 +74,37 @@ sdf_fd_gradient_kernel(const float* __restrict__ coords, int64_t n, SdfEvalField
             if (c == a) mine = g;
         }
         if (live && c < 3) grad[i * 3 + c] = mine;
+    }
+}
+
+// One marching iteration of PackedSDFTracer.trace (wisp/tracers/packed_sdf_tracer.py:118-146) including the field query
+// nef(coords=x, channels="sdf") of a NeuralSDF over an OctreeGrid (or the distance row of a NeuralSDFTex).  16 lanes own one
+// pack (= one ray that hit the octree): all 16 run the (pack-uniform) bookkeeping of sphere_trace_step (sphere_trace_dev.h),
+// lane 0 stores the state, and the packs still marching evaluate the field at the new position - the values wisp_sdf_query
+// returns there, bit for bit.  A group leaves as a whole, so nothing below the exits is wave-wide.
+template <typename T>
+__global__ void __launch_bounds__(SDFE_BLOCK)
+sdf_trace_fused_kernel(SphereTraceState st, int first, SdfEvalField fld, float scale, int32_t* __restrict__ any_active) {
+    extern __shared__ float s_sdfe[];
+    const SdfEvalLds s = sdf_eval_stage(s_sdfe, fld, 1);
+    const int c = threadIdx.x & (SDFE_GROUP - 1), grp = threadIdx.x / SDFE_GROUP;
+    const int64_t p = (int64_t)blockIdx.x * SDFE_GROUPS + grp;
+    if (p >= st.num_packs) return;
+    float px, py, pz;
+    bool m;
+    if (first) {
+        m = st.mask[p] != 0;
+        px = st.x[p * 3]; py = st.x[p * 3 + 1]; pz = st.x[p * 3 + 2];
+    } else {
+        m = sphere_trace_step(st, p, c == 0, px, py, pz);
+    }
+    if (!m) return;
+    if (c == 0 && any_active) atomicAdd(any_active, 1);
+    float o[1];
+    sdf_eval_point<T, 1>(fld, s, s.in + grp * SDFE_IN, c, px, py, pz, o);
+    if (c == 0) {
+#pragma clang fp contract(off)
+        st.dist[p] = o[0] * scale;
     }
 }
 
@@ -145,6 +179,32 @@ extern "C" int wisp_sdf_fd_gradient(const float* coords, int64_t n, const uint8_
     if (feats_dtype == WISP_F32) SDFE_GT(float); else if (feats_dtype == WISP_F16) SDFE_GT(__half); else SDFE_GT(__hip_bfloat16);
 #undef SDFE_GT
 #undef SDFE_G
+    WISP_CHECK_LAUNCH();
+    return WISP_OK;
+}
+
+extern "C" int wisp_sdf_trace_step_fused(int64_t num_packs, int first, const float* nug_o, const float* nug_d, const float* nug_depth,
+                                         const int32_t* nug_pidx, float dist_max, float thr_close, float thr_avg, float* t,
+                                         float* dist, float* dist_prev, uint8_t* mask, uint8_t* hit, const int32_t* curr_in,
+                                         int32_t* curr_out, int64_t* curr_pidx, float* x, const uint8_t* octree,
+                                         const int32_t* exsum, const int16_t* points, const int32_t* trinkets,
+                                         const void* const* feats, int feats_dtype, const int32_t* levels, int num_lods,
+                                         int channels, int half_round, const float* w1, const float* b1, const float* w2,
+                                         const float* b2, int hidden, float scale, int32_t* any_active, wisp_stream_t stream) {
+    WISP_REQUIRE(num_packs >= 0, "bad sizes");
+    SdfEvalField fld;
+    if (const int rc = sdf_eval_fill(fld, __func__, octree, exsum, points, trinkets, feats, feats_dtype, levels, num_lods, channels,
+                                     half_round, w1, b1, w2, b2, hidden, 1)) return rc;
+    if (num_packs == 0) return WISP_OK;
+    const SphereTraceState st{num_packs, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev,
+                              mask, hit, curr_in, curr_out, curr_pidx, x};
+    WISP_REQUIRE(sphere_trace_state_complete(st), "null pointer");
+    const size_t lds = sdf_eval_lds_bytes(hidden, 1, SDFE_GROUPS);
+    const dim3 grid((unsigned)ceil_div64(num_packs, SDFE_GROUPS)), block(SDFE_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+#define SDFE_T(T) hipLaunchKernelGGL((sdf_trace_fused_kernel<T>), grid, block, lds, s, st, first, fld, scale, any_active)
+    if (feats_dtype == WISP_F32) SDFE_T(float); else if (feats_dtype == WISP_F16) SDFE_T(__half); else SDFE_T(__hip_bfloat16);
+#undef SDFE_T
     WISP_CHECK_LAUNCH();
     return WISP_OK;
 }

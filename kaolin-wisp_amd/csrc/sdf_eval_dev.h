@@ -1,14 +1,16 @@
 // Field evaluation of the nglod shape as one __device__ function: NeuralSDF / NeuralSDFTex over an OctreeGrid
 // (wisp/models/nefs/neural_sdf.py:120-155, neural_sdf_tex.py:85-123: OctreeGrid.interpolate 'sum' over the active levels ->
-// [position, features] -> Linear -> relu -> Linear).  Shared by the kernels of sdf_eval.hip, so that a value the gradient kernel
-// differences is bit for bit the value the query kernel returns for the same position.
+// [position, features] -> Linear -> relu -> Linear).  The only evaluator of this shape outside training: the query, gradient
+// and marching kernels of sdf_eval.hip all call it, so that a value the gradient kernel differences, or a distance the march
+// advances by, is bit for bit the value the query kernel returns for the same position.
 //
 // 16 lanes own one point.  They walk the octree once (the voxel on every active level; a point outside [-1,1]^3 or in an
 // unoccupied cell gets zero features and the decoder still runs, as grid.interpolate + decoder do); lane c gathers feature
-// channel c of the 8 corners per level; the hidden layer is split over the lanes (weights in LDS), the ROWS output dot
-// products are reduced over the group with four shuffles each.  Query, trilinear weights and level sum restate
-// sdf_trace_fused_kernel (csrc/spc_interp.hip), whose statements are those of spc_query_kernel /
-// spc_trilinear_multi_fwd_kernel; the decoder is an fp32 fma chain in input order.
+// channel c of the 8 corners per level: one contiguous 64-byte row per corner and group; the hidden layer is split over the
+// lanes (weights in LDS), the ROWS output dot products are reduced over the group with four shuffles each.  Walk, trilinear
+// weights and level sum follow spc_query_kernel (csrc/spc.hip) / spc_trilinear_multi_fwd_kernel (csrc/spc_interp.hip), so
+// cells and features are those of the modular path; the decoder is an fp32 fma chain in input order, which differs from the
+// library GEMM of the modular path by summation order only.
 #pragma once
 #include "wisp_common.h"
 
@@ -72,8 +74,9 @@ static __device__ __forceinline__ void sdf_eval_coeffs(const float (&c)[3], cons
     for (int j = 0; j < 8; ++j) w[j] = (((j & 4) ? f[0] : g[0]) * ((j & 2) ? f[1] : g[1])) * ((j & 1) ? f[2] : g[2]);
 }
 
-// All 16 lanes of a group call this together, with the same position; every lane of the wave must be here (the reduction
-// shuffles).  c = lane within the group, gin = the group's 19 floats of LDS.  On return every lane holds the ROWS raw decoder
+// All 16 lanes of a group call this together, with the same position: the reduction shuffles have width 16 and the barriers
+// order one group's LDS traffic, so the wave's other groups need not be here (a marching kernel's group leaves early as a
+// whole).  c = lane within the group, gin = the group's 19 floats of LDS.  On return every lane holds the ROWS raw decoder
 // outputs (bias added) in the order the module produces them.
 template <typename T, int ROWS>
 static __device__ __forceinline__ void sdf_eval_point(const SdfEvalField& fld, const SdfEvalLds& s, float* gin, int c,

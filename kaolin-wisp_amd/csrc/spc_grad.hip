@@ -757,8 +757,9 @@ extern "C" int wisp_codebook_trilinear_multi_bwd(const float* coords, const int6
 // The reference issues ~60 kernels for it (a query, six trilinear lookups, two GEMMs with their elementwise companions, the
 // loss, and all of that again backwards); the modular path of this package 20.  At 512 coordinates every one of them is
 // launch latency.  Here:
-//   sdf_train_kernel     16 lanes per (sample, level) walk the octree to the level's cell and blend its corners (the statements
-//                        of sdf_trace_fused_kernel: bit-identical features; all levels of a sample at once, so the dependent
+//   sdf_train_kernel     16 lanes per (sample, level) walk the octree to the level's cell and blend its corners (its own copy
+//                        of the statements of spc_query_kernel / spc_trilinear_multi_fwd_kernel - inference has them in
+//                        sdf_eval_point, sdf_eval_dev.h; all levels of a sample at once, so the dependent
 //                        loads of the walk cost the deepest level's, not the sum); then 16 lanes per sample run the decoder
 //                        forward, d loss / d pred and the decoder backward: lane c keeps hidden units c, c + 16, ..., the
 //                        gradient of the decoder input is a column sum over LDS.  Per workgroup the weight gradients are

@@ -1377,23 +1377,16 @@ def sphere_trace_step(nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, th
 
 
 def sdf_trace_step_fused(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit,
-                         curr_in, curr_out, curr_pidx, x, octree, exsum, points, trinkets, feats, levels, half_round, w1, b1, w2, b2,
-                         scale, any_active=None):
-    """sphere_trace_step + the NeuralSDF / OctreeGrid field query at the new positions, one launch (csrc/spc_interp.hip)."""
-    P = nug_o.shape[0]
-    n = len(feats)
-    for f in feats:
-        assert f.is_cuda and f.is_contiguous() and f.dtype == feats[0].dtype and f.shape[1] == feats[0].shape[1]
-    fp = (ctypes.c_void_p * n)(*[f.data_ptr() for f in feats])
-    lv = (ctypes.c_int32 * n)(*[int(l) for l in levels])
-    for a in (w1, b1, w2, b2):
-        assert a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()
-    _check(lib.wisp_sdf_trace_step_fused(P, int(first), _p(nug_o), _p(nug_d), _p(nug_depth), _p(nug_pidx), float(np.float32(dist_max)),
-                                         float(np.float32(thr_close)), float(np.float32(thr_avg)), _p(t), _p(dist), _p(dist_prev),
-                                         _p(mask), _p(hit), _p(curr_in), _p(curr_out), _p(curr_pidx), _p(x), _p(octree), _p(exsum),
-                                         _p(points), _p(trinkets), fp, _DTYPE_CODE[feats[0].dtype], lv, n, feats[0].shape[1],
-                                         int(half_round), _p(w1), _p(b1), _p(w2), _p(b2), w1.shape[0], float(np.float32(scale)),
-                                         _p(any_active), _stream()), "sdf_trace_step_fused")
+                         curr_in, curr_out, curr_pidx, x, fld, scale, any_active=None):
+    """sphere_trace_step + the NeuralSDF / OctreeGrid field query at the new positions, one launch (csrc/sdf_eval.hip); fld: a
+    one-row field dict of PackedSDFTracer._fused_field (a textured field marches on its distance row)."""
+    args, keep = _sdf_field_args(fld)
+    assert args[-1] == 1, "the march takes one output row"
+    _check(lib.wisp_sdf_trace_step_fused(nug_o.shape[0], int(first), _p(nug_o), _p(nug_d), _p(nug_depth), _p(nug_pidx),
+                                         float(np.float32(dist_max)), float(np.float32(thr_close)), float(np.float32(thr_avg)),
+                                         _p(t), _p(dist), _p(dist_prev), _p(mask), _p(hit), _p(curr_in), _p(curr_out),
+                                         _p(curr_pidx), _p(x), *args[:-1], float(np.float32(scale)), _p(any_active), _stream()),
+           "sdf_trace_step_fused")
 
 
 def _sdf_field_args(fld):
@@ -1485,12 +1478,9 @@ def hash_sdf_trace_step_fused(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max
 def sdf_trace_step_field(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit,
                          curr_in, curr_out, curr_pidx, x, fld, scale, any_active=None):
     """One fused marching iteration on a field dict of PackedSDFTracer._fused_field: the entry point goes by its `kind`."""
-    state = (first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit, curr_in, curr_out,
-             curr_pidx, x)
-    if _is_hash_field(fld):
-        return hash_sdf_trace_step_fused(*state, fld, scale, any_active)
-    return sdf_trace_step_fused(*state, fld["octree"], fld["exsum"], fld["points"], fld["trinkets"], fld["feats"], fld["levels"],
-                                fld["half_round"], fld["w1"], fld["b1"], fld["w2"], fld["b2"], scale, any_active)
+    step = hash_sdf_trace_step_fused if _is_hash_field(fld) else sdf_trace_step_fused
+    return step(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit, curr_in,
+                curr_out, curr_pidx, x, fld, scale, any_active)
 
 
 _sdf_scratch = _Scratch(zeroed=False)      # (SDFTrainStep.capture bakes its address into a HIP graph: _Scratch keeps it alive)

@@ -74,6 +74,16 @@ class PackedSDFTracer(BaseTracer):
 
     # ------------------------------------------------------------------ fused iteration (field query inside the launch)
     @staticmethod
+    def _fused_decoder(nef, outputs):
+        """the decoder shape every fused march is built for: one hidden relu Linear of at most 256 units and an output
+        Linear of `outputs` rows, both with bias, no skip connection"""
+        dec = nef.decoder
+        return (nef.activation_type == 'relu' and nef.num_layers == 1 and len(dec.layers) == 1 and not dec.skip
+                and type(dec.layers[0]) is torch.nn.Linear and type(dec.lout) is torch.nn.Linear
+                and dec.layers[0].bias is not None and dec.lout.bias is not None and dec.lout.out_features == outputs
+                and dec.layers[0].out_features <= 256)
+
+    @staticmethod
     def _fused_field(nef, lod_idx):
         """The tensors wisp_sdf_trace_step_fused needs, or None when the field is not the shape it is built for: a plain
         NeuralSDF (nglod_octree.yaml) - OctreeGrid with 16 'sum'-med feature channels, linear interpolation, raw position
@@ -99,10 +109,7 @@ class PackedSDFTracer(BaseTracer):
         g, dec = nef.grid, nef.decoder
         if (g.multiscale_type != 'sum' or g.interpolation_type != 'linear' or g.feature_dim != 16 or lod_idx < 1
                 or not nef.position_input or not isinstance(nef.pos_embedder, torch.nn.Identity)
-                or nef.activation_type != 'relu' or nef.num_layers != 1 or len(dec.layers) != 1 or dec.skip
-                or type(dec.layers[0]) is not torch.nn.Linear or type(dec.lout) is not torch.nn.Linear
-                or dec.layers[0].bias is None or dec.lout.bias is None or dec.lout.out_features != 1
-                or dec.layers[0].out_features > 256 or not g.features[0].is_cuda):
+                or not PackedSDFTracer._fused_decoder(nef, 1) or not g.features[0].is_cuda):
             return None
         n = lod_idx + 1
         feats = [g.features[i].detach().contiguous() for i in range(n)]
@@ -123,10 +130,7 @@ class PackedSDFTracer(BaseTracer):
         if (g.multiscale_type != 'sum' or g.interpolation_type != 'linear' or g.feature_dim != 16 or lod_idx < 1
                 or (with_pos and not (isinstance(nef.pos_embedder, torch.nn.Identity) and nef.pos_embed_dim == 3))
                 or (not with_pos and nef.embedder_type != 'none')
-                or nef.activation_type != 'relu' or nef.num_layers != 1 or len(dec.layers) != 1 or dec.skip
-                or type(dec.layers[0]) is not torch.nn.Linear or type(dec.lout) is not torch.nn.Linear
-                or dec.layers[0].bias is None or dec.lout.bias is None or dec.lout.out_features != 4
-                or dec.layers[0].out_features > 256 or dec.layers[0].in_features != (3 if with_pos else 0) + 16
+                or not PackedSDFTracer._fused_decoder(nef, 4) or dec.layers[0].in_features != (3 if with_pos else 0) + 16
                 or not g.features[0].is_cuda):
             return None
         n = lod_idx + 1
@@ -157,10 +161,7 @@ class PackedSDFTracer(BaseTracer):
                 or not 1 <= g.num_lods <= 16 or not 0 <= lod_idx < g.num_lods
                 or (g.num_lods * g.feature_dim if g.multiscale_type == 'cat' else g.feature_dim) > 32
                 or not nef.position_input or not isinstance(nef.pos_embedder, torch.nn.Identity)
-                or nef.activation_type != 'relu' or nef.num_layers != 1 or len(dec.layers) != 1 or dec.skip
-                or type(dec.layers[0]) is not torch.nn.Linear or type(dec.lout) is not torch.nn.Linear
-                or dec.layers[0].bias is None or dec.lout.bias is None or dec.lout.out_features != 1
-                or dec.layers[0].out_features > 256 or not tables.is_cuda
+                or not PackedSDFTracer._fused_decoder(nef, 1) or not tables.is_cuda
                 or tables.dtype not in (torch.float32, torch.float16, torch.bfloat16)):
             return None
         cat = g.multiscale_type == 'cat'

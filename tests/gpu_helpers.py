@@ -46,6 +46,31 @@ def make_rays(n, seed, radius=3.0, spread=0.6):
     return o, d
 
 
+# ------------------------------------------------------------------------------------------------ one marching iteration
+def shell_blas(level, radius, width):
+    n = 2 ** level
+    idx = np.stack(np.meshgrid(*[np.arange(n)] * 3, indexing='ij'), -1).reshape(-1, 3)
+    ctr = (idx + 0.5) / (n / 2) - 1
+    cells = idx[np.abs(np.linalg.norm(ctr, axis=1) - radius) < width]
+    from wisp.accelstructs import OctreeAS
+    return cells, OctreeAS.from_quantized_points(torch.from_numpy(cells).short().to(DEV), level)
+
+
+def march_start(nef, n_rays, seed):
+    """the tracer's own start of a march: raytrace, first-hit marking, state"""
+    from wisp.core import Rays
+    from wisp.tracers import PackedSDFTracer
+    o, d = make_rays(n_rays, seed, radius=2.5, spread=0.7)
+    rays = Rays(torch.from_numpy(o).to(DEV), torch.from_numpy(d).to(DEV), dist_min=0.0, dist_max=6.0)
+    rt = nef.grid.raytrace(rays, nef.grid.blas.max_level, with_exit=True)
+    depth = rt.depth
+    depth[..., 0:1] += 1e-5
+    return rays, rt, depth, PackedSDFTracer._start(rays, rt.ridx, rt.pidx, depth)
+
+
+STATE = ("t", "dist", "dist_prev", "active", "hit", "nug", "cell", "x")     # the arrays of a _MarchState a marching iteration writes
+
+
 def sparse_tree(level, n, seed):
     rng = np.random.default_rng(seed)
     oc = ospc.points_to_octree(rng.integers(0, 2 ** level, size=(n, 3)), level)

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import hash_sdf_eval_ref as R
-from gpu_helpers import make_rays
+from gpu_helpers import STATE, make_rays, march_start, shell_blas
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -214,30 +214,6 @@ def test_iou_counts(res, hidden, F, multiscale, lod_idx, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ 4. one marching iteration
-def shell_blas(level, radius, width):
-    n = 2 ** level
-    idx = np.stack(np.meshgrid(*[np.arange(n)] * 3, indexing='ij'), -1).reshape(-1, 3)
-    ctr = (idx + 0.5) / (n / 2) - 1
-    cells = idx[np.abs(np.linalg.norm(ctr, axis=1) - radius) < width]
-    from wisp.accelstructs import OctreeAS
-    return cells, OctreeAS.from_quantized_points(torch.from_numpy(cells).short().to(DEV), level)
-
-
-def march_start(nef, n_rays, seed):
-    """the tracer's own start of a march: raytrace, first-hit marking, state"""
-    from wisp.core import Rays
-    from wisp.tracers import PackedSDFTracer
-    o, d = make_rays(n_rays, seed, radius=2.5, spread=0.7)
-    rays = Rays(torch.from_numpy(o).to(DEV), torch.from_numpy(d).to(DEV), dist_min=0.0, dist_max=6.0)
-    rt = nef.grid.raytrace(rays, nef.grid.blas.max_level, with_exit=True)
-    depth = rt.depth
-    depth[..., 0:1] += 1e-5
-    return rays, rt, depth, PackedSDFTracer._start(rays, rt.ridx, rt.pidx, depth)
-
-
-STATE = ("t", "dist", "dist_prev", "active", "hit", "nug", "cell", "x")
-
-
 @pytest.mark.parametrize("multiscale,dtype", [('cat', F32), ('sum', F16)])
 def test_fused_marching_iteration_equals_step_then_query_bit_for_bit(multiscale, dtype):
     """wisp_hash_sdf_trace_step_fused against wisp_sphere_trace_step followed by wisp_hash_sdf_query at x of the active packs

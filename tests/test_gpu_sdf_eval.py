@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import sdf_eval_ref as R
+from gpu_helpers import STATE, march_start
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -257,6 +258,69 @@ def test_gradient_is_the_central_difference_of_the_querys_own_values(kind, hidde
         assert float(u.max()) <= GRAD_MARGIN, (kind, n, float(u.max()))
         assert float(u64.max()) <= GRAD_MARGIN, (kind, n, float(u64.max()))
     assert float(want.abs().max()) > 1e-3
+
+
+# ------------------------------------------------------------------------------------------------ one marching iteration
+@pytest.mark.parametrize("kind,hidden,half,dtype,lod_idx", [("sdf", 128, True, torch.float32, 2), ("sdf", 17, False, torch.float16, 1),
+                                                            ("tex_pos", 128, True, torch.float32, 2)])
+def test_fused_marching_iteration_equals_step_then_query_bit_for_bit(kind, hidden, half, dtype, lod_idx):
+    """wisp_sdf_trace_step_fused against wisp_sphere_trace_step followed by wisp_sdf_query at x of the active packs times scale,
+    from a real raytrace of 300 rays through the level-4 shell: every state array bitwise equal after the first launch and after
+    each of 24 iterations - both sides run sphere_trace_step and sdf_eval_point.  A textured field marches on row 3 of its output
+    layer (PackedSDFTracer._fused_field_tex); its query side takes column 3 of the four-row field."""
+    import copy
+    from wisp.ops.sdf import fused_sdf_field
+    from wisp.tracers import PackedSDFTracer
+    import wisp._C as C
+    sh, nef, _, _ = generic_setup(kind, hidden, half, dtype, lod_idx, n=1)
+    rays, rt, depth, st0 = march_start(nef, 300, 151)
+    P = st0.t.shape[0]
+    assert 100 < P <= 300
+    march = PackedSDFTracer._fused_field(nef, lod_idx)
+    rows = fused_sdf_field(nef, lod_idx)
+    assert march is not None and march["b2"].numel() == 1 and rows["b2"].numel() == (1 if kind == "sdf" else 4)
+    v = C.sdf_query(st0.x, march)                                        # distances of about a cell's size, mostly positive
+    march = dict(march, b2=march["b2"] - float(v.median()) + 0.15)
+    b2 = rows["b2"].clone()
+    b2[-1] = march["b2"][0]
+    rows = dict(rows, b2=b2)
+    scale, min_dis, dist_max = 0.8, 0.0003, float(rays.dist_max)
+    a, b = copy.deepcopy(st0), copy.deepcopy(st0)
+    counter = torch.zeros(1, dtype=torch.int32, device=DEV)
+
+    def fused(st, first, cnt=None):
+        C.sdf_trace_step_field(first, st.o, st.d, depth, rt.pidx, dist_max, min_dis, min_dis * 5, st.t, st.dist, st.dist_prev,
+                               st.active, st.hit, st.nug, st.nug_next, st.cell, st.x, march, scale, cnt)
+
+    def query(st):
+        sel = st.active.bool()
+        if bool(sel.any()):
+            st.dist[sel] = C.sdf_query(st.x[sel], rows)[:, -1] * scale
+
+    def same(where):
+        for name in STATE:
+            assert torch.equal(getattr(a, name), getattr(b, name)), (where, name)
+    fused(a, True)
+    query(b)
+    same("start")
+    a.dist_prev.copy_(a.dist)
+    b.dist_prev.copy_(b.dist)
+    for it in range(24):
+        counter.zero_()
+        fused(a, False, counter)
+        a.nug, a.nug_next = a.nug_next, a.nug
+        C.sphere_trace_step(b.o, b.d, depth, rt.pidx, dist_max, min_dis, min_dis * 5, b.t, b.dist, b.dist_prev, b.active, b.hit,
+                            b.nug, b.nug_next, b.cell, b.x)
+        b.nug, b.nug_next = b.nug_next, b.nug
+        query(b)
+        same(f"iteration {it}")
+        assert int(counter.item()) == int(b.active.sum())
+        if it == 0:
+            assert int(b.active.sum()) > 50 and not torch.equal(b.t, st0.t)
+    moved = int((b.nug != st0.nug).sum())
+    record("march_exact", kind=kind, hidden=hidden, half=int(half), dtype=str(dtype), lod_idx=lod_idx, packs=P,
+           active_after_24=int(b.active.sum()), hits=int(b.hit.sum()), moved_cells=moved)
+    assert int(b.active.sum()) < P and moved > 10                          # packs left or converged, and cells were jumped
 
 
 # ------------------------------------------------------------------------------------------------ fallback

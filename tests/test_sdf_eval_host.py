@@ -129,6 +129,34 @@ def test_argument_checks_are_returned_before_any_launch(gradient):
     assert f(*args) == -1
 
 
+def test_the_fused_marching_step_checks_its_field_like_the_query():
+    """wisp_sdf_trace_step_fused describes its field through the query's own checks (one output row): the same refusals, before
+    any launch and before the empty-march return"""
+    import wisp._C as C
+    f = C._cdll.wisp_sdf_trace_step_fused
+    null = ctypes.c_void_p(0)
+
+    def call(patch=None, levels=(2, 3, 4), packs=8, null_feat=False):
+        args, keep = _host_args(levels=levels)
+        for k, v in (patch or {}).items():
+            args[k] = v
+        if null_feat:
+            args[FEATS][1] = None
+        state = [null] * 13 if packs == 0 else [args[COORDS]] * 13      # nug_o .. nug_pidx, t .. x
+        return f(packs, 0, *state[:4], 6.0, 3e-4, 1.5e-3, *state[4:], *args[OCTREE:ROWS], 0.8, null, null)
+    assert call(packs=0) == 0                                                      # an empty march: only the field is looked at
+    for patch in ({CHANNELS: 8}, {CHANNELS: 32}, {HIDDEN: 0}, {HIDDEN: 257}, {LODS: 0}, {LODS: 17}):
+        for packs in (8, 0):
+            assert call(patch, packs=packs) == -1, (patch, packs)                  # WISP_ERR_INVALID
+            assert C.lib.wisp_last_error()
+    for levels in ((3, 2, 4), (2, 2, 4)):                                          # not ascending
+        assert call(levels=levels) == -1, levels
+    assert call(null_feat=True) == -1
+    assert call(packs=-1) == -1
+    args, keep = _host_args()
+    assert f(8, 0, *[args[COORDS]] * 3, null, 6.0, 3e-4, 1.5e-3, *[args[COORDS]] * 9, *args[OCTREE:ROWS], 0.8, null, null) == -1   # nug_pidx
+
+
 @pytest.mark.skipif(not kernel_meta.available(LIB), reason="libwisp_hip.so not built or llvm-readelf missing")
 def test_the_kernels_have_no_scratch():
     meta = kernel_meta.kernels(LIB)
