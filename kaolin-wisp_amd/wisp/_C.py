@@ -28,6 +28,7 @@ F32, F16, BF16 = 0, 1, 2
 _DTYPE_CODE = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
 c_vp, c_i64, c_i32, c_f32, c_u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
+c_f64 = ctypes.c_double
 
 # name -> argtypes (restype int unless listed in _RESTYPES); mirrors include/wisp_hip.h one to one
 SIGNATURES = {
@@ -169,10 +170,12 @@ SIGNATURES = {
     "wisp_image_field_train_scratch_bytes": [c_i64, c_i32, c_i32],
     "wisp_image_field_train_step": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "wisp_ssim_scratch_bytes": [c_i32, c_i32, c_i32],
+    "wisp_ssim": [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
-_RESTYPES = {"wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
+_RESTYPES = {"wisp_ssim_scratch_bytes": c_i64, "wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
              "wisp_last_error": ctypes.c_char_p, "wisp_host_reader_create": c_vp, "wisp_host_reader_destroy": None,
              "wisp_nerf_step_config_bytes": c_i64, "wisp_nerf_step_workspace_bytes": c_i64, "wisp_nerf_step_create": c_vp,
              "wisp_nerf_step_destroy": None}
@@ -1818,6 +1821,50 @@ def image_field_render(h, w, first, n, codebook, first_idx, resolutions, codeboo
                                        int(active_lods), int(codebook_bitwidth), _p(packed), int(hp), _p(gts_u8) if want_err else None,
                                        _p(out_f32), _p(out_u8), _p(part), _stream()), "image_field_render")
     return out_f32, out_u8, part
+
+
+_ssim_scratch = _Scratch(zeroed=False)
+
+
+def _ssim_view(t, channels, name):
+    """an [H, W, >= channels] image as the kernel addresses it: f32, on the GPU, channel stride 1, rows that do not overlap -
+    a view where it already is (the [..., :3] of an RGBA buffer, row-padded views), a contiguous copy otherwise"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"wisp HIP op: `{name}` must be a GPU tensor (the hot path has no CPU fallback); got "
+                           f"{type(t).__name__} on {getattr(t, 'device', None)}")
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    h, w = t.shape[0], t.shape[1]
+    sr, sp, sc = t.stride()
+    if sc != 1 or sp < channels or sr < (w - 1) * sp + channels or h * sr >= 2 ** 31:
+        t = t[..., :channels].contiguous()
+    return t
+
+
+def ssim(a, b, channels, weights, cov_norm, c1, c2, want_map=False):
+    """wisp_ssim (csrc/ssim.hip): a, b [H, W, >= channels] images on the GPU (f32; other float types are converted), `weights` the
+    2 radius + 1 window weights as a HOST float64 array -> (f64 [channels + 1]: the channel scores and their mean, f64
+    [H, W, channels] map or None).  Two launches (tiles, then their sum in a fixed order), nothing read back."""
+    if a.dim() != 3 or tuple(a.shape[:2]) != tuple(b.shape[:2]) or b.dim() != 3 or min(a.shape[2], b.shape[2]) < channels:
+        raise ValueError(f"ssim: needs two [H, W, >= {channels}] images of one size, got {tuple(a.shape)} / {tuple(b.shape)}")
+    a, b = _ssim_view(a, channels, "a"), _ssim_view(b, channels, "b")
+    if a.device != b.device:
+        raise RuntimeError(f"ssim: the images are on different devices ({a.device} / {b.device})")
+    w64 = np.ascontiguousarray(weights, dtype=np.float64)
+    radius = (w64.size - 1) // 2
+    h, w, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    if w64.size != 2 * radius + 1 or not 1 <= radius <= 15:
+        raise ValueError(f"ssim: the window must have 2 radius + 1 weights with radius in 1..15, got {w64.size}")
+    if h < w64.size or w < w64.size:
+        raise ValueError(f"ssim: a {h} x {w} image is smaller than the {w64.size} x {w64.size} window")
+    need = int(lib.wisp_ssim_scratch_bytes(h, w, int(channels)))
+    scratch = _ssim_scratch.get(dev, need)
+    out = torch.empty(channels + 1, dtype=torch.float64, device=dev)
+    smap = torch.empty(h, w, channels, dtype=torch.float64, device=dev) if want_map else None
+    _check(lib.wisp_ssim(_p(a), a.stride(0), a.stride(1), _p(b), b.stride(0), b.stride(1), h, w, int(channels), radius,
+                         w64.ctypes.data_as(c_vp), float(cov_norm), float(c1), float(c2), _p(out), _p(smap), _p(scratch),
+                         scratch.numel(), _stream()), "ssim")
+    return out, smap
 
 
 _image_train_scratch = _Scratch(zeroed=False)   # (ImageTrainStep.capture bakes its address into a HIP graph)

@@ -83,13 +83,18 @@ class ImageTrainer(BaseTrainer):
 
     def validate(self):
         """image_trainer.py:95-181 without its logging back-ends: render the image, PSNR against the ground truth, img_pred.png
-        and img_gts.png into the tracker's log directory, return_dict['psnr'] = the best so far."""
+        and img_gts.png into the tracker's log directory, return_dict[metric] = the best so far.  'ssim' (image_trainer.py:146-147)
+        compares the float image with bank / 255 through wisp.ops.image.ssim on the GPU - one more render, the PSNR and the PNGs
+        come from the same launch as without it; on any other device it is refused, as 'lpips' is everywhere."""
         from wisp.models.nefs.image_nef import fused_render_shape, render_image
-        from wisp.ops.image import psnr, save_u8
-        for name in ('ssim', 'lpips'):
-            if name in self.cfg.valid_metrics:
-                raise NotImplementedError(f"valid_metrics: {name!r} needs a package this project does not depend on "
-                                          f"({'scikit-image' if name == 'ssim' else 'lpips'}); only 'psnr' is provided")
+        from wisp.ops.image import psnr, save_u8, ssim
+        if 'lpips' in self.cfg.valid_metrics:
+            raise NotImplementedError("valid_metrics: 'lpips' needs a package this project does not depend on (lpips); "
+                                      "'psnr' and 'ssim' are provided")
+        want_ssim = 'ssim' in self.cfg.valid_metrics
+        if want_ssim and torch.device(self.device).type != 'cuda':
+            raise NotImplementedError(f"valid_metrics: 'ssim' is computed on the GPU (wisp.ops.image.ssim has no host path); "
+                                      f"this trainer's device is {self.device!r}")
         nef, ds = self.pipeline.nef, self.train_dataset
         nef.eval()
         h, w = ds.h, ds.w
@@ -101,11 +106,14 @@ class ImageTrainer(BaseTrainer):
             pred_u8, err = render_image(nef, h, w, out='u8', gts_u8=bank)
             if want_psnr:
                 metrics_dict['psnr'] = 10 * np.log10(1.0 / (float(err) / (h * w * 3)))
+            img = render_image(nef, h, w, out='f32').reshape(h, w, 3) if want_ssim else None
         else:
             img = render_image(nef, h, w, out='f32').reshape(h, w, 3)
             pred_u8 = (img * 255).byte()
             if want_psnr:
                 metrics_dict['psnr'] = psnr(img, bank / 255.0)
+        if want_ssim:
+            metrics_dict['ssim'] = ssim(img, bank.reshape(h, w, 3) / 255.0)
         os.makedirs(self.tracker.log_dir, exist_ok=True)
         save_u8(os.path.join(self.tracker.log_dir, 'img_pred.png'), pred_u8.reshape(h, w, 3).cpu().numpy())
         # (the reference writes (gts * 255).byte() of gts = u8 / 255: fl(fl(v / 255) * 255) truncates back to v for all 256 values)

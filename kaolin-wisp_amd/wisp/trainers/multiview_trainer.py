@@ -1066,17 +1066,21 @@ class MultiviewTrainer(BaseTrainer):
         through the tracker's visualizer (wisp.trainers.validation.render when the tracker has none), compared with its image
         through wisp.ops.image.psnr, and - with cfg.save_valid_imgs - written as val/{idx}-{name}.png under the tracker's log
         directory (the bytes of rb.image().byte().rgb).  The mean of each metric is logged in the reference's format, the best
-        value so far is kept in return_dict, and the dict of means is returned.  'ssim' and 'lpips' need packages this project
-        does not depend on; EXR needs pyexr and is skipped with the reference's one-time log line.
+        value so far is kept in return_dict, and the dict of means is returned.  'ssim' is wisp.ops.image.ssim, computed on the
+        GPU (csrc/ssim.hip): there is no host path, so on any other device it is refused before a view is rendered; 'lpips'
+        needs a package and weights this project does not have; EXR needs pyexr and is skipped with the reference's one-time
+        log line.
         The renders run in fp32 (as validate() does) with the tracer's fused_query on: lookup + decoder in one launch where the
         field allows it, the same bits as the modular path; the attribute is put back afterwards."""
         from wisp.core import RenderBuffer
-        from wisp.ops.image import psnr, write_png
+        from wisp.ops.image import psnr, ssim, write_png
         from wisp.trainers import validation
-        for metric in ('ssim', 'lpips'):
-            if metric in self.cfg.valid_metrics:
-                raise NotImplementedError(f"valid_metrics: {metric!r} needs a package this project does not depend on "
-                                          f"({'scikit-image' if metric == 'ssim' else 'lpips'}); only 'psnr' is provided")
+        if 'lpips' in self.cfg.valid_metrics:
+            raise NotImplementedError("valid_metrics: 'lpips' needs a package this project does not depend on (lpips); "
+                                      "'psnr' and 'ssim' are provided")
+        if 'ssim' in self.cfg.valid_metrics and torch.device(self.device).type != 'cuda':
+            raise NotImplementedError(f"valid_metrics: 'ssim' is computed on the GPU (wisp.ops.image.ssim has no host path); "
+                                      f"this trainer's device is {self.device!r}")
         valid_log_dir = os.path.join(self.tracker.log_dir, "val")
         img_shape = validation_dataset.img_shape
         data = validation_dataset.data
@@ -1099,6 +1103,8 @@ class MultiviewTrainer(BaseTrainer):
                 gts = img.reshape(*img_shape[:2], -1)
                 if 'psnr' in self.cfg.valid_metrics:
                     metrics_dict['psnr'] += psnr(rb.rgb[..., :3], gts[..., :3])
+                if 'ssim' in self.cfg.valid_metrics:
+                    metrics_dict['ssim'] += ssim(rb.rgb[..., :3], gts[..., :3])
                 out_name = f"{idx}"
                 if name is not None:
                     out_name += "-" + name
@@ -1123,10 +1129,11 @@ class MultiviewTrainer(BaseTrainer):
 
     def validate(self):
         """PSNR over the validation views (multiview_trainer.py:257-303 without the table writers).  With cfg.save_valid_imgs the
-        views also go to val/*.png, through evaluate_metrics."""
+        views also go to val/*.png, through evaluate_metrics; so does every valid_metrics that names more than 'psnr' (images
+        are still written only with save_valid_imgs)."""
         if self.validation_dataset is None:
             return None
-        if self.cfg.save_valid_imgs:
+        if self.cfg.save_valid_imgs or set(getattr(self.cfg, 'valid_metrics', ())) - {'psnr'}:
             self.pipeline.eval()
             lod_idx = self.pipeline.nef.grid.num_lods - 1
             self.evaluate_metrics(self.validation_dataset, lod_idx, name=f"lod{lod_idx}")

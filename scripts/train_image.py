@@ -3,7 +3,7 @@ ImageDataset (u8 bank on the GPU, fused sampling), HashGrid.from_geometric(blas=
 Adam (lr 1e-3, eps 1e-16, weight decay 1e-6), grid lr x 500 and the MultiStepLR schedule, validation (whole-image render, PSNR,
 img_pred.png / img_gts.png) at the end.
 
-    python scripts/train_image.py IMAGE [--epochs N] [--fused-step] [--fused-kernel] [--log-dir DIR]
+    python scripts/train_image.py IMAGE [--epochs N] [--fused-step] [--fused-kernel] [--valid-metrics psnr [ssim]] [--log-dir DIR]
     python scripts/train_image.py --write-test-image PATH [--size H W] ...
 
 --write-test-image PATH first writes a procedural RGB PNG to PATH and then fits it, so the script runs where no image exists.
@@ -12,7 +12,8 @@ graph) instead of ImageTrainer's torch.optim loop; validation is ImageTrainer's 
 --fused-kernel (implies --fused-step) builds ImageTrainStep(..., fused=True): forward + loss + backward run through
 wisp_image_field_train_step (csrc/image_field_train.hip, two launches) instead of the modular ops under autograd.
 The last line printed is one JSON record: PSNR after the first epoch and after training, seconds, ms per step, and
-fused_image_step - whether the steps went through that kernel."""
+fused_image_step - whether the steps went through that kernel.  --valid-metrics psnr ssim also computes the structural
+similarity of the final image (wisp.ops.image.ssim, on the GPU) and adds `ssim` to the record."""
 import argparse
 import json
 import logging
@@ -53,13 +54,14 @@ def build(image_path, device, num_pixels=4096, hidden_dim=64, codebook_bitwidth=
     return ds, Pipeline(nef=nef)
 
 
-def trainer_config(epochs, enable_amp=True, valid_every=-1):
+def trainer_config(epochs, enable_amp=True, valid_every=-1, valid_metrics=('psnr',)):
     from wisp.trainers import ConfigAdam, ConfigBaseTrainer
     return ConfigBaseTrainer(optimizer=ConfigAdam(lr=1e-3, eps=1e-16, weight_decay=1e-6), exp_name='image-hash', max_epochs=epochs,
-                             valid_every=valid_every, enable_amp=enable_amp, profile_nvtx=False, grid_lr_weight=500.0, scheduler=True)
+                             valid_every=valid_every, enable_amp=enable_amp, profile_nvtx=False, grid_lr_weight=500.0, scheduler=True,
+                             valid_metrics=tuple(valid_metrics))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("image", nargs="?")
     ap.add_argument("--write-test-image", metavar="PATH")
@@ -74,7 +76,16 @@ def main(argv=None):
     ap.add_argument("--log-dir", default=os.path.join("_results", "logs", "runs", "image-hash"))
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--valid-metrics", nargs="+", choices=("psnr", "ssim"), default=["psnr"],
+                    help="validation metrics (image_hash.yaml: psnr); ssim needs --device cuda")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if "psnr" not in args.valid_metrics:
+        ap.error("--valid-metrics must name psnr (the record's psnr fields come from it)")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     from wisp.ops.image import save_u8
     from wisp.trainers import ImageTrainer, ImageTrainStep
@@ -88,7 +99,7 @@ def main(argv=None):
         ap.error("give an IMAGE or --write-test-image PATH")
     torch.manual_seed(args.seed)
     ds, pipeline = build(path, args.device, args.num_pixels, args.hidden_dim, args.codebook_bitwidth)
-    trainer = ImageTrainer(trainer_config(args.epochs, enable_amp=not args.no_amp), pipeline, ds, tracker=_Tracker(args.log_dir),
+    trainer = ImageTrainer(trainer_config(args.epochs, enable_amp=not args.no_amp, valid_metrics=args.valid_metrics), pipeline, ds, tracker=_Tracker(args.log_dir),
                            device=args.device)
     steps_per_epoch = trainer.iterations_per_epoch
     total = steps_per_epoch * args.epochs
@@ -125,11 +136,13 @@ def main(argv=None):
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     seconds = time.time() - t0
-    final = trainer.validate()['psnr']
+    last = trainer.validate()
+    final = last['psnr']
+    extra = dict(ssim=float(last['ssim'])) if 'ssim' in last else {}
     print(json.dumps(dict(image=os.path.abspath(path), h=ds.h, w=ds.w, step="ImageTrainStep" if args.fused_step or args.fused_kernel else "ImageTrainer",
                           fused_image_step=fused_image_step,
                           epochs=args.epochs, steps=total, psnr_first_epoch=first, psnr=final, seconds=round(seconds, 3),
-                          ms_per_step=round(1e3 * seconds / total, 4), log_dir=os.path.abspath(args.log_dir))))
+                          ms_per_step=round(1e3 * seconds / total, 4), log_dir=os.path.abspath(args.log_dir), **extra)))
     return final
 
 

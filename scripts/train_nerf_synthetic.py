@@ -2,7 +2,7 @@
 app/nerf/main_nerf.py:74-116 with this package's classes - NeRFSyntheticDataset + SampleRays, create_split for validation, the
 nerf_hash.yaml pipeline, MultiviewTrainer, validation PSNR.
 
-    python scripts/train_nerf_synthetic.py DATASET_DIR [--epochs N] [--mip M] [--valid-split val]
+    python scripts/train_nerf_synthetic.py DATASET_DIR [--epochs N] [--mip M] [--valid-split val] [--valid-metrics psnr [ssim]]
     python scripts/train_nerf_synthetic.py --write-synlego DIR [--views 100] [--res 800]
 
 With --write-synlego DIR a SynLego scene (synlego.py's analytic brick assembly) is first written to DIR in the NeRF-synthetic
@@ -94,7 +94,7 @@ def build_pipeline(device, num_steps=2048, bg_color=(0.0, 0.0, 0.0)):
     return Pipeline(nef, PackedRFTracer(raymarch_type='ray', num_steps=num_steps, step_size=1.0, bg_color=tuple(bg_color)))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("dataset_dir", nargs="?", help="dataset root (transforms*.json + images)")
     ap.add_argument("--write-synlego", metavar="DIR", default=None, help="write a SynLego scene to DIR first and train on it")
@@ -107,7 +107,16 @@ def main(argv=None):
     ap.add_argument("--num-steps", type=int, default=2048, help="raymarch steps (nerf_hash.yaml: 2048)")
     ap.add_argument("--valid-split", default="val")
     ap.add_argument("--bg", type=float, nargs=3, default=(0.0, 0.0, 0.0))
+    ap.add_argument("--valid-metrics", nargs="+", choices=("psnr", "ssim"), default=["psnr"],
+                    help="validation metrics (nerf_hash.yaml: psnr); with ssim the record carries the views' mean SSIM too")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if "psnr" not in args.valid_metrics:
+        ap.error("--valid-metrics must name psnr (the record's psnr comes from it)")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     assert torch.cuda.is_available(), "train_nerf_synthetic.py trains on the GPU"
     dev = "cuda:0"
@@ -131,13 +140,15 @@ def main(argv=None):
     pipeline = build_pipeline(dev, args.num_steps, args.bg)
     cfg = ConfigMultiviewTrainer(optimizer=ConfigAdamW(lr=1e-3, eps=1e-16, weight_decay=1e-6), grid_lr_weight=500.0, enable_amp=True,
                                  prune_every=100, rgb_loss_type='huber', rgb_loss_denom='rays', max_epochs=args.epochs, scheduler=True,
-                                 valid_every=-1, save_every=-1, profile_nvtx=False)
+                                 valid_every=-1, save_every=-1, profile_nvtx=False, valid_metrics=tuple(args.valid_metrics))
     trainer = MultiviewTrainer(cfg, pipeline, train, validation_dataset=valid, device=dev)
     t0 = time.perf_counter()
     trainer.train()
     torch.cuda.synchronize()
     print(f"trained {args.epochs} epochs ({trainer.total_iterations} iterations) in {time.perf_counter() - t0:.1f}s")
-    print(json.dumps(dict(metric="train_nerf_synthetic", views=len(train), epochs=args.epochs, psnr=float(trainer.validate()["psnr"]))))
+    result = trainer.validate()
+    extra = dict(ssim=float(result["ssim"])) if "ssim" in result else {}
+    print(json.dumps(dict(metric="train_nerf_synthetic", views=len(train), epochs=args.epochs, psnr=float(result["psnr"]), **extra)))
 
 
 if __name__ == "__main__":
