@@ -892,14 +892,16 @@ sdf_train_kernel(const float* __restrict__ coords, const float* __restrict__ gts
                 for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
                 const float r = fmaxf(a, 0.0f);
                 out = __builtin_fmaf(s_w2[hh], r, out);
-                ga[hh] = a > 0.0f ? s_w2[hh] : 0.0f;    // finished below, once d loss / d pred is known
+                ga[hh] = a > 0.0f ? 1.0f : 0.0f;        // the relu mask; finished below, once d loss / d pred is known
                 gr[hh] = r;
             }
 #pragma unroll
             for (int d = ST_GROUP / 2; d >= 1; d >>= 1) out += __shfl_xor(out, d, ST_GROUP);
             const float diff = (out + b2) - gts[s];
             g = 2.0f * diff * inv_batch;                 // d [sum (pred - gt)^2 / B] / d pred
-            for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] *= g; gr[hh] *= g; }
+            // (the relu's backward SELECTS, as in sdf_tex_train_kernel: a unit that is off passes 0 on, also for a non-finite g,
+            //  where a product with the mask would be 0 * inf = NaN)
+            for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = ga[hh] != 0.0f ? s_w2[hh] * g : 0.0f; gr[hh] *= g; }
             if (c == 0) { s_g[grp] = g; s_sq[grp] = diff * diff; }
         } else if (grp < spb) {
             for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = 0.0f; gr[hh] = 0.0f; }

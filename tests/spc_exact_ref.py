@@ -34,11 +34,14 @@ LEVELS4 = (2, 3, 4, 5)
 
 # ---------------------------------------------------------------------------------------------------- the tree
 class Tree:
-    """octree of `n` random points at `level` (the recipe of gpu_helpers._sparse_blas) with its dual corners"""
+    """octree of `n` random points at `level` (the recipe of gpu_helpers._sparse_blas) with its dual corners; `extra`: further
+    cells [m, 3] of `level` that the octree holds as well"""
 
-    def __init__(self, level=5, n=3000, seed=401):
+    def __init__(self, level=5, n=3000, seed=401, extra=None):
         rng = np.random.default_rng(seed)
         P = rng.integers(0, 2 ** level, size=(n, 3))
+        if extra is not None:
+            P = np.concatenate([P, np.asarray(extra, dtype=P.dtype).reshape(-1, 3)])
         self.level, self.n, self.seed = level, n, seed
         self.octree = ospc.points_to_octree(P, level)
         self.points, self.pyramid, self.exsum = ospc.octree_to_spc(self.octree)

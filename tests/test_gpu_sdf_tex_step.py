@@ -57,7 +57,8 @@ def test_fused_textured_step_matches_the_cpu_oracle(shell, B, lods, H, pos):
     """wisp_sdf_tex_train_step against autograd through the CPU oracle: oracle.octree_grid.octree_grid_interpolate ('sum', the
     reference's fp16 rounding) -> [position, features] or the features alone -> Linear -> relu -> Linear(H, 4) -> sigmoid on the
     first three -> (sum (rgb - rgb_gt)^2 + sum (sdf - gt)^2) / B: the loss, the two un-normalised sums and every gradient.
-    (37 coordinates over 3 levels: 5 samples per pass with an idle lane group; 24 hidden units: no multiple of 16.)"""
+    (37 coordinates over 3 levels: 5 samples per pass with an idle lane group; 24 hidden units: no multiple of 16.)
+    The tolerances here scale with a tensor's largest entry; element-wise correctness is owned by tests/test_gpu_sdf_step_exact.py."""
     from oracle import octree_grid as og
     from wisp.trainers import SDFTrainStep
     nef = _tex_field(shell["blas"], pos, lods=lods, hidden=H, seed=13)
