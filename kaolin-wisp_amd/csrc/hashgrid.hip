@@ -1203,6 +1203,9 @@ static int64_t queue_emitter_grid_cap(int resident_per_cu) {
     return per_cu > 0 ? (int64_t)per_cu * cus : 0;
 }
 
+// reduce workgroups per coarse level (a level of at most 32 buckets) for a launch of n samples - measured, see bin_plan
+static int64_t coarse_level_wgs(int64_t n) { return n >= ((int64_t)1 << 21) ? 64 : 16; }
+
 // bin geometry shared by the workspace query and the launcher
 struct BinPlan { int chunk_shift, max_chunks, max_splits, total_blocks, total_ranks, emit_threads /* queue emitter width, 0 = generic emitter */; int64_t ntiles; BinLevels bins; int64_t count_bytes, record_bytes; bool ok;
                  uint32_t base_cap[HG_MAX_LODS]; };
@@ -1288,8 +1291,14 @@ static BinPlan bin_plan(int64_t n, const HashLevels& lv, const LevelList& levels
         // the 50^3 and 64^3 levels could take the optimizer's step in the flush too: their single workgroups walk 512 nearly empty
         // slots each and became the launch's long pole - 0.41 -> 0.49 ms; profiles/r05_ab_single_owner_mid_levels.txt.)
         // (64 is the measured optimum at 2^21 samples: 16 / 32 / 128 / 256 workgroups per coarse level run the pair in 0.445 / 0.431 /
-        //  0.426 / 0.456 ms against 0.416)
-        int splits = (int)(64 / chunks);
+        //  0.426 / 0.456 ms against 0.416.  At 2^18 samples an owner has an eighth of the records to walk and every workgroup still
+        //  holds a whole CU for its chain of loads: 8 / 16 / 32 workgroups per coarse level run the step in 0.321 / 0.318 / 0.320 ms
+        //  against 0.325; at 2^20 and at 1.5 x 2^20 samples 16 and 64 run the step alike, 0.633-0.637 and 0.824-0.830 ms either way -
+        //  coarse_level_wgs, profiles/reduce_coarse_wgs_ab.txt.)
+        // A level that 64 would split stays split (at least 2 owners): covered_rows - and with it the caller's optimizer ranges -
+        // only knows "one owner" and "several", and single-owner mid levels are the launch's long pole (round 5, above).
+        int splits = (int)(coarse_level_wgs(n) / chunks);
+        if (splits < 2 && chunks <= 32) splits = 2;
         if (splits > p.ntiles) splits = (int)p.ntiles;
         p.bins.splits[li] = splits < 1 ? 1 : splits;
         if (chunks > p.max_chunks) p.max_chunks = (int)chunks;

@@ -25,6 +25,11 @@
 namespace {
 
 constexpr int NS_TIMED_KERNELS = 4;                   // hashgrid_fwd, nerf_mlp_fwd, nerf_mlp_bwd, hashgrid_bwd
+// Six events time the four: where one interval ends at the point of the stream the next starts from (lookup -> decoder forward,
+// decoder backward -> hash-grid backward) ONE event is both - every hipEventRecord between two launches costs ~6 us of idle GPU.
+constexpr int NS_STEP_EVENTS = 6;
+constexpr int NS_EV_BEGIN[NS_TIMED_KERNELS] = {0, 1, 3, 4};
+constexpr int NS_EV_END[NS_TIMED_KERNELS] = {1, 2, 4, 5};
 constexpr int NS_MAX_TIMED_STEPS = 512;                // event pairs are created with the handle: recording must not pay for them
 constexpr int NS_LOSS_RING = 8;
 
@@ -181,8 +186,8 @@ extern "C" void* wisp_nerf_step_create(const wisp_nerf_step_config* cfg, void* w
         }
     }
     // the timing events exist from the start (hipEventCreate inside a timed step would be part of what it measures)
-    s->ev.reserve((size_t)NS_MAX_TIMED_STEPS * 2 * NS_TIMED_KERNELS);
-    for (int i = 0; i < NS_MAX_TIMED_STEPS * 2 * NS_TIMED_KERNELS; ++i) {
+    s->ev.reserve((size_t)NS_MAX_TIMED_STEPS * NS_STEP_EVENTS);
+    for (int i = 0; i < NS_MAX_TIMED_STEPS * NS_STEP_EVENTS; ++i) {
         hipEvent_t e;
         if (hipEventCreate(&e) != hipSuccess) break;
         s->ev.push_back(e);
@@ -271,8 +276,8 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
 
     hipEvent_t* ev = nullptr;
     if (record_timing && s->timed_steps < NS_MAX_TIMED_STEPS &&
-        s->ev.size() >= (size_t)(s->timed_steps + 1) * 2 * NS_TIMED_KERNELS) {          // (a full record: later steps go untimed)
-        ev = s->ev.data() + (size_t)s->timed_steps * 2 * NS_TIMED_KERNELS;
+        s->ev.size() >= (size_t)(s->timed_steps + 1) * NS_STEP_EVENTS) {          // (a full record: later steps go untimed)
+        ev = s->ev.data() + (size_t)s->timed_steps * NS_STEP_EVENTS;
         s->ev_units[s->timed_steps] = S;
         ++s->timed_steps;
     }
@@ -294,14 +299,13 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
     NS_MARK(0);
     NS_CALL(wisp_hashgrid_interpolate_fwd(samples, S, 3, c.table_lookup, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
                                           c.num_lods, c.bitwidth, c.zero_from_col, feats, st));
-    NS_MARK(1);
-    NS_MARK(2);
+    NS_MARK(1);                                        // end of the lookup = start of the decoder forward
     if (image)
         NS_CALL(wisp_nerf_mlp_fwd_rays_img(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, image, color,
                                            density, st));
     else
         NS_CALL(wisp_nerf_mlp_fwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, color, density, st));
-    NS_MARK(3);
+    NS_MARK(2);
     // The step's two closing sums - the loss partials into the loss slot, the decoder's dW partial rows into dec_grad - are launches
     // of their own (inside wisp_composite_loss / wisp_nerf_mlp_bwd_rays*), or with hp->tail_fold side workgroups of the hash-grid reduce
     // launch (wisp_step_tail): nothing reads either result before the optimizer launch behind it.
@@ -321,7 +325,7 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
                                     comp_ws, s->lay.comp_ws_floats, st));
     }
     // ---- backward
-    NS_MARK(4);
+    NS_MARK(3);
     if (tail_fold) {
         if (image)
             NS_CALL(wisp_nerf_mlp_bwd_rays_img_partials(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, image,
@@ -338,9 +342,8 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
         NS_CALL(wisp_nerf_mlp_bwd_rays(feats, c.dtype_table, code, ridx, S, c.in_dim, c.hidden, c.view_freqs, c.dec_params, g_color, g_density,
                                        g_feats, c.dec_grad, mlp_ws, s->lay.mlp_ws_bytes, st));
     }
-    NS_MARK(5);
     int64_t covered[16] = {0};
-    NS_MARK(6);
+    NS_MARK(4);                                        // end of the decoder backward = start of the hash-grid backward
     if (tail_fold) {
         int tail_done = 0;
         NS_CALL(wisp_hashgrid_interpolate_bwd_adamw_tail(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
@@ -362,7 +365,7 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
         NS_CALL(wisp_hashgrid_interpolate_bwd(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions, c.num_lods,
                                               c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace, hashgrid_workspace_bytes,
                                               level_cap_scale, st));
-    NS_MARK(7);
+    NS_MARK(5);
     if (covered_rows)
         for (int l = 0; l < c.num_lods; ++l) covered_rows[l] = covered[l];
 
@@ -411,10 +414,10 @@ extern "C" int wisp_nerf_step_read_timing(void* step, int max_steps, float* ms /
     Step* s = static_cast<Step*>(step);
     const int n = s->timed_steps < max_steps ? s->timed_steps : max_steps;
     for (int i = 0; i < n; ++i) {
-        hipEvent_t* ev = s->ev.data() + (size_t)i * 2 * NS_TIMED_KERNELS;
+        hipEvent_t* ev = s->ev.data() + (size_t)i * NS_STEP_EVENTS;
         for (int k = 0; k < NS_TIMED_KERNELS; ++k) {
             float t = 0.0f;
-            const hipError_t e = hipEventElapsedTime(&t, ev[2 * k], ev[2 * k + 1]);      // (needs the events complete: synchronise first)
+            const hipError_t e = hipEventElapsedTime(&t, ev[NS_EV_BEGIN[k]], ev[NS_EV_END[k]]);      // (needs the events complete: synchronise first)
             if (e != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, __func__, hipGetErrorString(e));
             ms[(size_t)i * NS_TIMED_KERNELS + k] = t;
         }
