@@ -8,8 +8,8 @@
 // 512 coordinates every one of those launches is launch latency.  Here, two launches:
 //   hash_sdf_train_kernel         16 lanes own a sample.  The forward is hash_sdf_eval_point's two halves (hash_sdf_eval_dev.h),
 //                                 statement for statement: the predicted distance is bit for bit what wisp_hash_sdf_query returns
-//                                 for the same parameters.  Then g = 2 (pred - gt) / B and the decoder backward as in
-//                                 sdf_train_kernel: lane c keeps hidden units c, c + 16, ..., the gradient of the decoder's
+//                                 for the same parameters.  Then g = 2 (pred - gt) / B and the decoder backward as in the
+//                                 one-output sdf_train_kernel<1>: lane c keeps hidden units c, c + 16, ..., the gradient of the decoder's
 //                                 feature columns is a column sum over LDS.  The table gradient is scattered right there: the lane
 //                                 that blended a column pair recomputes its corner_setup (the same bits) and adds coef[j] * dfeat
 //                                 to the pair's eight rows of grad_codebook with f32 atomic adds - the form of hashgrid_bwd_kernel
@@ -18,8 +18,8 @@
 //                                 feature gradient.  Per workgroup the decoder's weight gradients and the squared error are summed
 //                                 by the thread that owns the entry, in sample order, and stored as one partial row - no atomics.
 //   hash_sdf_train_reduce_kernel  adds the partial rows up in workgroup order, ADDS the sums to the decoder's gradient tensors,
-//                                 writes the loss (sdf_train_reduce_kernel's scheme; that kernel lives in another translation
-//                                 unit and sums in fp32).
+//                                 writes the loss (sdf_train_reduce_kernel's scheme for one output; that kernel lives in
+//                                 another translation unit, serves the octree steps of both fields and sums in fp32).
 // The sums over hidden units, samples and partial rows run in fp64 and are rounded to fp32 once each (products of two floats are
 // exact in fp64): that keeps every gradient as close to the float64 result as the modular path's library GEMMs are.
 // A level of at most 2^16 table entries - the coarse ones, where many samples of a batch meet on a row - takes its gradient through

@@ -557,18 +557,20 @@ static bool sg_use_flags(const SgCall& c, const SgPlan& pl) { return c.n * 8 * c
 // all levels one after the other with the rest of the chip idle
 static int sg_split_lods(const SgCall& c) { return c.num_lods > 1 && c.n * (c.channels <= 64 ? c.channels : 64) < (int64_t)256 * 1024; }
 
-// passes 1 and 2
-static int sg_scatter(const SgCall& c, const SgLods& ml, const SgPlan& pl, unsigned char* ws, hipStream_t s) {
+// passes 1 and 2; have_absmax: the caller has zeroed the header and a kernel of its own leaves the magnitude bound there (pass 1)
+static int sg_scatter(const SgCall& c, const SgLods& ml, const SgPlan& pl, unsigned char* ws, hipStream_t s, bool have_absmax = false) {
     SgHeader* hdr = reinterpret_cast<SgHeader*>(ws);
     uint8_t* flags = sg_use_flags(c, pl) ? ws + pl.off_flags : nullptr;
     long long* acc = reinterpret_cast<long long*>(ws + pl.off_acc);
     const int clog = sg_clog(c.n);
-    if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return -1;
-    const unsigned g1 = (unsigned)min64(ceil_div64(c.n, 256), 4096);
+    if (!have_absmax) {
+        if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return -1;
+        const unsigned g1 = (unsigned)min64(ceil_div64(c.n, 256), 4096);
 #define SG_ABSMAX(I) hipLaunchKernelGGL((spc_grad_absmax_kernel<I>), dim3(g1), dim3(256), 0, s, c.coords, (const I*)c.cells,   \
                                         c.cell_stride, c.spv, c.points, ml, c.grad_out, c.n, c.num_lods, c.channels, c.sum, hdr)
-    if (c.cells_is_i64) SG_ABSMAX(int64_t); else SG_ABSMAX(int32_t);
+        if (c.cells_is_i64) SG_ABSMAX(int64_t); else SG_ABSMAX(int32_t);
 #undef SG_ABSMAX
+    }
     if (c.channels <= 8) {
         const dim3 grid((unsigned)ceil_div64(c.n, SG_THREADS)), block(SG_THREADS);
 #define SG_MERGE(FF, I) hipLaunchKernelGGL((spc_grad_scatter_merge_kernel<FF, I>), grid, block, 0, s, c.coords, (const I*)c.cells, \
@@ -607,6 +609,17 @@ static int sg_fill(SgLods& ml, const int32_t* levels, const int64_t* rows, int n
     return 0;
 }
 
+// pass 3 of the feature tables
+static void sg_finalize(const SgCall& c, const SgLods& ml, const SgPlan& pl, unsigned char* ws, hipStream_t s) {
+    int lpr = 1;
+    while (lpr < c.channels && lpr < 64) lpr <<= 1;
+    const unsigned g3 = (unsigned)min64(ceil_div64(pl.total_rows, 256 / lpr), 8192);
+    if (pl.total_rows > 0)
+        hipLaunchKernelGGL(spc_grad_finalize_kernel, dim3(g3), dim3(256), 0, s, ml, c.num_lods, c.channels, pl.stride, lpr,
+                           sg_clog(c.n), reinterpret_cast<const SgHeader*>(ws), sg_use_flags(c, pl) ? ws + pl.off_flags : nullptr,
+                           reinterpret_cast<long long*>(ws + pl.off_acc));
+}
+
 static int spc_bwd_impl(const SgCall& c, const int32_t* levels, const int64_t* rows, float* const* grad_feats, void* workspace,
                         int64_t workspace_bytes, hipStream_t s) {
     SgLods ml;
@@ -619,13 +632,7 @@ static int spc_bwd_impl(const SgCall& c, const int32_t* levels, const int64_t* r
     if (!workspace || workspace_bytes < pl.bytes) return wisp_fail(WISP_ERR_INVALID, __func__, "workspace missing or too small (wisp_spc_bwd_workspace_bytes)");
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     if (sg_scatter(c, ml, pl, ws, s) != 0) return wisp_fail(WISP_ERR_LAUNCH, __func__, "hipMemsetAsync failed");
-    int lpr = 1;
-    while (lpr < c.channels && lpr < 64) lpr <<= 1;
-    const unsigned g3 = (unsigned)min64(ceil_div64(pl.total_rows, 256 / lpr), 8192);
-    if (pl.total_rows > 0)
-        hipLaunchKernelGGL(spc_grad_finalize_kernel, dim3(g3), dim3(256), 0, s, ml, c.num_lods, c.channels, pl.stride, lpr,
-                           sg_clog(c.n), reinterpret_cast<const SgHeader*>(ws), sg_use_flags(c, pl) ? ws + pl.off_flags : nullptr,
-                           reinterpret_cast<long long*>(ws + pl.off_acc));
+    sg_finalize(c, ml, pl, ws, s);
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, __func__, hipGetErrorString(e_));
     return WISP_OK;
@@ -750,394 +757,163 @@ extern "C" int wisp_codebook_trilinear_multi_bwd(const float* coords, const int6
 }
 
 // ---------------------------------------------------------------------------------------------- fused SDF regression step
-// One optimisation step of the reference's SDFTrainer (wisp/trainers/sdf_trainer.py:65-124, only_last) for a NeuralSDF over an
-// OctreeGrid (wisp/models/nefs/neural_sdf.py:102-155; nglod_octree.yaml: 16 'sum' features on 6 levels, [position, features]
-// -> Linear(19, 128) -> relu -> Linear(128, 1), 512 coordinates per step):
+// One optimisation step of the reference's SDFTrainer (wisp/trainers/sdf_trainer.py:65-124, only_last) over an OctreeGrid, for
+// both of its fields.  A NeuralSDF (wisp/models/nefs/neural_sdf.py:102-155; nglod_octree.yaml: 16 'sum' features on 6 levels,
+// [position, features] -> Linear(19, 128) -> relu -> Linear(128, 1), 512 coordinates per step) has one decoder output:
 //     pred = decoder([x, sum_l trilinear_l(x)]) ;  loss = sum (pred - gt)^2 / B ;  backward
-// The reference issues ~60 kernels for it (a query, six trilinear lookups, two GEMMs with their elementwise companions, the
-// loss, and all of that again backwards); the modular path of this package 20.  At 512 coordinates every one of them is
+// A NeuralSDFTex (neural_sdf_tex.py:95-123, sample_tex) has four, rgb = sigmoid(y[0:3]), sdf = y[3], the position is optional:
+//     in = pos_input ? [x, f] : f ;  loss = (sum (rgb - rgb_gt)^2 + sum (sdf - gt)^2) / B
+// The reference issues ~60 kernels for the step (a query, six trilinear lookups, two GEMMs with their elementwise companions,
+// the loss, and all of that again backwards); the modular path of this package 20.  At 512 coordinates every one of them is
 // launch latency.  Here:
-//   sdf_train_kernel     16 lanes per (sample, level) walk the octree to the level's cell and blend its corners (its own copy
-//                        of the statements of spc_query_kernel / spc_trilinear_multi_fwd_kernel - inference has them in
-//                        sdf_eval_point, sdf_eval_dev.h; all levels of a sample at once, so the dependent
-//                        loads of the walk cost the deepest level's, not the sum); then 16 lanes per sample run the decoder
-//                        forward, d loss / d pred and the decoder backward: lane c keeps hidden units c, c + 16, ..., the
-//                        gradient of the decoder input is a column sum over LDS.  Per workgroup the weight gradients are
-//                        summed by the thread that owns the entry, in sample order, and stored as one partial row - no atomics.  The
-//                        sample's feature gradient [16] and cell chain go to scratch; the workgroup's largest |w g| goes to
-//                        the header of the order-free scatter below, which therefore needs no magnitude pass of its own.
-//   sdf_train_reduce     adds the partial rows up in workgroup order, ADDS the sums to the decoder's gradient tensors, writes
-//                        the loss.
-//   spc_grad_scatter_wide + spc_grad_finalize   the corner sums of all six levels (64-bit fixed point, above).
-// Every sum has a fixed order or is an integer sum: the step is bitwise repeatable.
+//   sdf_train_kernel<NOUT>  one kernel for NOUT = 1 or 4 decoder outputs; only the loss head is written per field.
+//                        Phase 1 (st_lookup): 16 lanes per (sample, level) walk the octree to the level's cell and blend its
+//                        corners (all levels of a sample at once, so the dependent loads of the walk cost the deepest level's,
+//                        not the sum; inference has the same statements in sdf_eval_point, sdf_eval_dev.h).  Phase 2: 16 lanes
+//                        per sample run the decoder forward, d loss / d y (g = 2 diff / B; through the sigmoid, g_o = 2 diff_o
+//                        c_o (1 - c_o) / B) and the decoder backward: lane c keeps hidden units c, c + 16, ..., d
+//                        pre-activation[h] = (a_h > 0) sum_o W2[o][h] g_o in ascending o, the gradient of the decoder input
+//                        is a column sum over LDS.  Phase 3: the weight gradients and squared errors of the workgroup are
+//                        summed by the thread that owns the entry, in sample order, and stored as one partial row - no
+//                        atomics.  The sample's feature gradient [16] and cell chain go to scratch; the workgroup's largest
+//                        |w g| goes to the header of the order-free scatter, which therefore needs no magnitude pass.
+//   sdf_train_reduce_kernel  adds the partial rows up in workgroup order, ADDS the sums to the decoder's gradient tensors, writes
+//                        the loss: loss[0] = sum / B for one output, loss[3] = {total / B, distance sum, colour sum} for four.
+//   spc_grad_scatter_wide + spc_grad_finalize   the corner sums of all levels (64-bit fixed point, above).
+// Every sum has a fixed order or is an integer sum: the step is bitwise repeatable.  The two instantiations round apart in two
+// places only, kept on purpose and marked "rounding" below: with inert colour rows (W2[0:3] = 0, b2[0:3] = 0, colour target
+// 0.5: g_0..2 = 0 exactly) every sum that reaches dW1, db1 and the feature tables is the one-output instantiation's, term by
+// term in the same order, and those gradients are bitwise equal.
 #define ST_GROUP 16
 #define ST_GROUPS 16                       // samples per workgroup pass
 #define ST_MAX_HIDDEN 256
-#define ST_MAX_IN 32
 
 struct StField {
     const float* feats[SG_MAX_LODS];
     int32_t level[SG_MAX_LODS];
-    int num_lods, channels, half_round, hidden, max_level;
-    const float *w1, *b1, *w2, *b2;
-};
-
-static __device__ __forceinline__ int st_child_slot(int qx, int qy, int qz, int sh) {
-    return (((qx >> sh) & 1) << 2) | (((qy >> sh) & 1) << 1) | ((qz >> sh) & 1);
-}
-
-__global__ void __launch_bounds__(ST_GROUP * ST_GROUPS)
-sdf_train_kernel(const float* __restrict__ coords, const float* __restrict__ gts, int64_t n, const uint8_t* __restrict__ octree,
-                 const int32_t* __restrict__ exsum, const int16_t* __restrict__ points, const int32_t* __restrict__ trinkets,
-                 StField fld, float inv_batch, float* __restrict__ partials /* [grid][row] */, int row_stride,
-                 float* __restrict__ dfeat /* [n][channels] */, int64_t* __restrict__ chain /* [n][num_lods] */,
-                 SgHeader* __restrict__ hdr) {
-    extern __shared__ float s_st[];
-    const int C = fld.channels, H = fld.hidden, NL = fld.num_lods;
-    const int in_dim = 3 + C;
-    const int in_pad = in_dim | 1;                      // odd row stride: the lanes of a group read different rows
-    const int spb = ST_GROUPS / NL;                     // samples per workgroup pass: one lane group per (sample, level)
-    float* s_w1 = s_st;                                 // [H][in_pad]
-    float* s_b1 = s_w1 + H * in_pad;                    // [H]
-    float* s_w2 = s_b1 + H;                             // [H]
-    float* s_in = s_w2 + H;                             // [spb][in_dim]        decoder inputs of the pass
-    float* s_ga = s_in + ST_GROUPS * in_dim;            // [spb][H]             d loss / d pre-activation
-    float* s_gr = s_ga + ST_GROUPS * H;                 // [spb][H]             d loss / d pred * relu output (for d w2)
-    float* s_g = s_gr + ST_GROUPS * H;                  // [spb]                d loss / d pred
-    float* s_sq = s_g + ST_GROUPS;                      // [spb]                squared error
-    float* s_lev = s_sq + ST_GROUPS;                    // [groups][C]          one level's lookup of one sample
-    float* s_wm = s_lev + ST_GROUPS * ST_GROUP;         // [groups]             its largest corner weight
-    for (int e = threadIdx.x; e < H * in_dim; e += blockDim.x) s_w1[(e / in_dim) * in_pad + e % in_dim] = fld.w1[e];
-    for (int e = threadIdx.x; e < H; e += blockDim.x) { s_b1[e] = fld.b1[e]; s_w2[e] = fld.w2[e]; }
-    const int c = threadIdx.x & (ST_GROUP - 1);
-    const int grp = threadIdx.x / ST_GROUP;
-    const int L = fld.max_level;
-    const float b2 = fld.b2[0];
-    // partial sums of this workgroup: d W1 [H][in_dim], d b1 [H], d w2 [H], d b2, loss - in that order; every entry has one owner
-    const int n_entries = H * in_dim + 2 * H + 2;
-    float* s_own = s_wm + ST_GROUPS;                    // [n_entries]
-    for (int e = threadIdx.x; e < n_entries; e += blockDim.x) s_own[e] = 0.0f;
-    uint32_t mbits = 0;
-    const int my_si = grp / NL, my_li = grp - my_si * NL;                 // phase 1: this group's (sample of the pass, level)
-    __syncthreads();
-    for (int64_t base = (int64_t)blockIdx.x * spb; base < n; base += (int64_t)gridDim.x * spb) {
-        // ---- phase 1: every (sample, level) pair on its own lane group: walk to the level's cell, trilinear lookup.  The walk
-        //      is a chain of dependent loads; six groups walking at once cost the time of the deepest one
-        {
-            const int64_t s = base + my_si;
-            float acc = 0.0f, wm = 0.0f;
-            if (my_si < spb && s < n) {
-                const float px = coords[s * 3], py = coords[s * 3 + 1], pz = coords[s * 3 + 2];
-                const bool inside = (fabsf(px) <= 1.0f) && (fabsf(py) <= 1.0f) && (fabsf(pz) <= 1.0f);
-                const float res = (float)(1 << L);
-                const int top = (1 << L) - 1;
-                const int qx = min((int)floorf(res * (0.5f * px + 0.5f)), top);
-                const int qy = min((int)floorf(res * (0.5f * py + 0.5f)), top);
-                const int qz = min((int)floorf(res * (0.5f * pz + 0.5f)), top);
-                const float pos[3] = {px, py, pz};
-                const int lv = fld.level[my_li];
-                int64_t node = inside ? 0 : -1;
-                for (int l = 0; l < lv && node >= 0; ++l) {               // (spc_query_kernel's walk)
-                    const int cs = st_child_slot(qx, qy, qz, L - 1 - l);
-                    const uint32_t bits = octree[node];                   // both loads of a level go out together: one round
-                    const int64_t first = (int64_t)exsum[node];           // trip per level, not two
-                    const int64_t child = first + __popc(bits & ((2u << cs) - 1u));
-                    node = ((bits >> cs) & 1u) ? child : -1;
-                }
-                if (c == 0) chain[s * NL + my_li] = node;
-                if (node >= 0) {
-                    float w[8];
-                    sg_coeffs(pos, points + node * 3, lv, w);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) wm = fmaxf(wm, fabsf(w[j]));
-                    const int32_t* tr = trinkets + node * 8;
-                    const float* f = fld.feats[my_li];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        float fv = f[(int64_t)tr[j] * C + c];
-                        if (fld.half_round) fv = __half2float(__float2half_rn(fv));
-                        acc += fv * w[j];
-                    }
-                    if (fld.half_round) acc = __half2float(__float2half_rn(acc));
-                }
-            }
-            s_lev[grp * ST_GROUP + c] = acc;
-            if (c == 0) s_wm[grp] = wm;
-        }
-        __syncthreads();
-        // ---- phase 2: group si owns sample si of the pass: decoder forward, d loss / d pred, decoder backward
-        const int64_t s = base + grp;
-        const bool live = grp < spb && s < n;
-        float* gin = s_in + grp * in_dim;
-        float* ga = s_ga + grp * H;
-        float* gr = s_gr + grp * H;
-        float wmax = 0.0f;
-        if (live) {
-            float feat = 0.0f;                                            // channel c, summed over the levels in order
-            for (int li = 0; li < NL; ++li) {
-                feat += s_lev[(grp * NL + li) * ST_GROUP + c];
-                wmax = fmaxf(wmax, s_wm[grp * NL + li]);
-            }
-            if (c < 3) gin[c] = coords[s * 3 + c];
-            gin[3 + c] = feat;
-        }
-        __builtin_amdgcn_wave_barrier();                 // a group's lanes are in one wave: LDS order suffices
-        float g = 0.0f;
-        if (live) {
-            // decoder forward: in = [position, features] (neural_sdf.py: embedded position first)
-            float out = 0.0f;
-            for (int hh = c; hh < H; hh += ST_GROUP) {
-                const float* wr = s_w1 + hh * in_pad;
-                float a = s_b1[hh];
-                for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
-                const float r = fmaxf(a, 0.0f);
-                out = __builtin_fmaf(s_w2[hh], r, out);
-                ga[hh] = a > 0.0f ? 1.0f : 0.0f;        // the relu mask; finished below, once d loss / d pred is known
-                gr[hh] = r;
-            }
-#pragma unroll
-            for (int d = ST_GROUP / 2; d >= 1; d >>= 1) out += __shfl_xor(out, d, ST_GROUP);
-            const float diff = (out + b2) - gts[s];
-            g = 2.0f * diff * inv_batch;                 // d [sum (pred - gt)^2 / B] / d pred
-            // (the relu's backward SELECTS, as in sdf_tex_train_kernel: a unit that is off passes 0 on, also for a non-finite g,
-            //  where a product with the mask would be 0 * inf = NaN)
-            for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = ga[hh] != 0.0f ? s_w2[hh] * g : 0.0f; gr[hh] *= g; }
-            if (c == 0) { s_g[grp] = g; s_sq[grp] = diff * diff; }
-        } else if (grp < spb) {
-            for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = 0.0f; gr[hh] = 0.0f; }
-            if (c < 3) gin[c] = 0.0f;
-            gin[3 + c] = 0.0f;
-            if (c == 0) { s_g[grp] = 0.0f; s_sq[grp] = 0.0f; }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (live) {
-            // gradient of the decoder input, feature columns only (nothing consumes d / d position)
-            float dx = 0.0f;
-            for (int hh = 0; hh < H; ++hh) dx = __builtin_fmaf(ga[hh], s_w1[hh * in_pad + 3 + c], dx);
-            dfeat[s * C + c] = dx;
-            const uint32_t b = __float_as_uint(wmax * fabsf(dx)) & 0x7fffffffu;
-            const uint32_t nb = (!(dx == dx) || !(wmax == wmax)) ? 0x7fc00000u : b;
-            mbits = nb > mbits ? nb : mbits;
-        }
-        __syncthreads();
-        // ---- phase 3: weight gradients of this pass: the thread that owns an entry adds the samples up in order
-        for (int e = threadIdx.x; e < n_entries; e += blockDim.x) {
-            float acc = 0.0f;
-            if (e < H * in_dim) {
-                const int hh = e / in_dim, i = e - hh * in_dim;
-                for (int q = 0; q < spb; ++q) acc = __builtin_fmaf(s_ga[q * H + hh], s_in[q * in_dim + i], acc);
-            } else if (e < H * in_dim + H) {
-                const int hh = e - H * in_dim;
-                for (int q = 0; q < spb; ++q) acc += s_ga[q * H + hh];
-            } else if (e < H * in_dim + 2 * H) {
-                const int hh = e - H * in_dim - H;
-                for (int q = 0; q < spb; ++q) acc += s_gr[q * H + hh];
-            } else if (e == H * in_dim + 2 * H) {
-                for (int q = 0; q < spb; ++q) acc += s_g[q];
-            } else {
-                for (int q = 0; q < spb; ++q) acc += s_sq[q];
-            }
-            s_own[e] += acc;
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < n_entries; e += blockDim.x) partials[(int64_t)blockIdx.x * row_stride + e] = s_own[e];
-    mbits = sg_wave_umax(mbits);
-    if ((threadIdx.x & 63) == 0 && mbits > __atomic_load_n(&hdr->absmax_bits, __ATOMIC_RELAXED)) atomicMax(&hdr->absmax_bits, mbits);
-}
-
-__global__ void __launch_bounds__(256)
-sdf_train_reduce_kernel(const float* __restrict__ partials, int rows, int row_stride, int H, int in_dim, float* __restrict__ gw1,
-                        float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2, float* __restrict__ loss,
-                        float inv_batch) {
-    // 16 lanes per entry: lane r adds rows r, r + 16, ... in order, then a fixed butterfly over the 16 lanes
-    const int n_entries = H * in_dim + 2 * H + 2;
-    const int r0 = threadIdx.x & 15;
-    for (int e = blockIdx.x * 16 + (threadIdx.x >> 4); e < n_entries + 15; e += gridDim.x * 16) {      // (whole groups stay together)
-        const bool in = e < n_entries;
-        float acc = 0.0f;
-        if (in)
-            for (int r = r0; r < rows; r += 16) acc += partials[(int64_t)r * row_stride + e];
-#pragma unroll
-        for (int d = 8; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 16);
-        if (!in || r0 != 0) continue;
-        if (e < H * in_dim) gw1[e] += acc;
-        else if (e < H * in_dim + H) gb1[e - H * in_dim] += acc;
-        else if (e < H * in_dim + 2 * H) gw2[e - H * in_dim - H] += acc;
-        else if (e == H * in_dim + 2 * H) gb2[0] += acc;
-        else loss[0] = acc * inv_batch;
-    }
-}
-
-static inline int st_grid(int64_t n, int num_lods) { return (int)min64(ceil_div64(n, ST_GROUPS / num_lods), 1024); }
-static inline int st_row_stride(int hidden, int channels) { return (hidden * (3 + channels) + 2 * hidden + 2 + 15) / 16 * 16; }
-
-extern "C" int64_t wisp_sdf_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden) {
-    if (n < 0 || num_lods < 1 || num_lods > SG_MAX_LODS || channels < 1 || hidden < 1) return -1;
-    return (int64_t)st_grid(n, num_lods) * st_row_stride(hidden, channels) * 4 + sg_round64(n * channels * 4) + n * num_lods * 8;
-}
-
-extern "C" int wisp_sdf_train_step(const float* coords, const float* gts, int64_t n, const uint8_t* octree, const int32_t* exsum,
-                                   const int16_t* points, const int32_t* trinkets, const float* const* feats,
-                                   const int32_t* levels, const int64_t* rows, int num_lods, int channels, int half_round,
-                                   const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
-                                   float* const* grad_feats, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
-                                   float* loss, void* scratch, int64_t scratch_bytes, void* workspace, int64_t workspace_bytes,
-                                   wisp_stream_t stream) {
-    WISP_REQUIRE(n >= 1 && num_lods >= 1 && num_lods <= SG_MAX_LODS, "bad sizes");
-    WISP_REQUIRE(channels == ST_GROUP, "the fused SDF step is built for 16 feature channels (nglod_octree.yaml)");
-    WISP_REQUIRE(hidden >= 1 && hidden <= ST_MAX_HIDDEN, "hidden width out of range");
-    WISP_REQUIRE(coords && gts && octree && exsum && points && trinkets && feats && levels && rows && w1 && b1 && w2 && b2 &&
-                 grad_feats && grad_w1 && grad_b1 && grad_w2 && grad_b2 && loss && scratch && workspace, "null pointer");
-    WISP_REQUIRE(scratch_bytes >= wisp_sdf_train_scratch_bytes(n, num_lods, channels, hidden), "scratch too small (wisp_sdf_train_scratch_bytes)");
-    StField fld;
-    SgLods ml;
-    WISP_REQUIRE(sg_fill(ml, levels, rows, num_lods) == 0, "bad level or row count");
-    for (int l = 0; l < num_lods; ++l) {
-        WISP_REQUIRE(feats[l] && grad_feats[l] && (l == 0 || levels[l] > levels[l - 1]), "bad level list");
-        fld.feats[l] = feats[l]; fld.level[l] = levels[l]; ml.grad[l] = grad_feats[l];
-    }
-    fld.num_lods = num_lods; fld.channels = channels; fld.half_round = half_round; fld.hidden = hidden;
-    fld.max_level = levels[num_lods - 1];
-    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
-    const SgPlan pl = sg_plan(ml.base[num_lods], channels, 0);
-    WISP_REQUIRE(workspace_bytes >= pl.bytes, "workspace too small (wisp_spc_bwd_workspace_bytes)");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    SgHeader* hdr = reinterpret_cast<SgHeader*>(ws);
-    const int grid = st_grid(n, num_lods), row_stride = st_row_stride(hidden, channels), in_dim = 3 + channels;
-    float* partials = static_cast<float*>(scratch);
-    float* dfeat = partials + (size_t)grid * row_stride;
-    int64_t* chain = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(dfeat) + sg_round64(n * channels * 4));
-    const size_t lds = ((size_t)hidden * (in_dim | 1) + 2 * hidden + (size_t)ST_GROUPS * (in_dim + 2 * hidden + 2 + ST_GROUP + 1) +
-                        (size_t)hidden * in_dim + 2 * hidden + 2) * 4;
-    const float inv_batch = 1.0f / (float)n;
-    if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, __func__, "hipMemsetAsync failed");
-    if (const hipError_t e = WISP_ALLOW_LDS(sdf_train_kernel, lds)) return wisp_fail(WISP_ERR_LAUNCH, __func__, hipGetErrorString(e));
-    hipLaunchKernelGGL(sdf_train_kernel, dim3(grid), dim3(ST_GROUP * ST_GROUPS), lds, s, coords, gts, n, octree, exsum, points,
-                       trinkets, fld, inv_batch, partials, row_stride, dfeat, chain, hdr);
-    hipLaunchKernelGGL(sdf_train_reduce_kernel, dim3((hidden * in_dim + 2 * hidden + 2 + 15) / 16), dim3(256), 0, s,
-                       partials, grid, row_stride, hidden, in_dim, grad_w1, grad_b1, grad_w2, grad_b2, loss, inv_batch);
-    // the corner sums: the magnitude bound is in the header already (sdf_train_kernel), so only scatter + row pass
-    SgCall c{coords, chain, 1, num_lods, 1, points, trinkets, dfeat, n, num_lods, channels, 1, channels};
-    uint8_t* flags = sg_use_flags(c, pl) ? ws + pl.off_flags : nullptr;
-    long long* acc = reinterpret_cast<long long*>(ws + pl.off_acc);
-    const int clog = sg_clog(n);
-    const int split = sg_split_lods(c);
-    hipLaunchKernelGGL((spc_grad_scatter_wide_kernel<int64_t>),
-                       dim3((unsigned)min64(ceil_div64(n * (split ? num_lods : 1), 256 / channels), 16384)), dim3(256), 0, s, coords, chain,
-                       (int64_t)num_lods, 1, points, trinkets, ml, dfeat, n, num_lods, channels, 1, clog, pl.stride, channels, hdr, flags,
-                       acc, split);
-    int lpr = 1;
-    while (lpr < channels && lpr < 64) lpr <<= 1;
-    if (pl.total_rows > 0)
-        hipLaunchKernelGGL(spc_grad_finalize_kernel, dim3((unsigned)min64(ceil_div64(pl.total_rows, 256 / lpr), 8192)), dim3(256), 0, s, ml,
-                           num_lods, channels, pl.stride, lpr, clog, hdr, flags, acc);
-    WISP_CHECK_LAUNCH();
-    return WISP_OK;
-}
-
-// ------------------------------------------------------------------------------------- fused textured SDF regression step
-// The same step for a NeuralSDFTex (wisp/models/nefs/neural_sdf_tex.py:95-123; sdf_trainer.py:65-124 with sample_tex and
-// only_last): the decoder has four outputs, rgb = sigmoid(y[0:3]), sdf = y[3], and the embedded position is optional:
-//     in = pos_input ? [x, f] : f ;  loss = (sum (rgb - rgb_gt)^2 + sum (sdf - gt)^2) / B
-//   sdf_tex_train_kernel         phase 1 is sdf_train_kernel's, statement for statement (bit-identical features); phase 2 keeps
-//                                four output dot products per lane, reduces them by the same butterfly, and forms
-//                                g_o = 2 diff_o sigmoid'(y_o) / B (colour), g_3 = 2 diff_3 / B (distance),
-//                                d pre-activation[h] = (a_h > 0) sum_o W2[o][h] g_o in ascending o; phase 3 owns
-//                                dW1 [H][in_dim], db1 [H], dW2 [4][H], db2 [4] and three scalars (squared distance error,
-//                                squared colour error, their total), one thread per entry, samples in order.
-//   sdf_tex_train_reduce_kernel  adds the partial rows in workgroup order, ADDS to the gradient tensors, writes
-//                                loss[3] = {total / B, distance sum, colour sum}.
-// With inert colour rows (W2[0:3] = 0, b2[0:3] = 0, colour target 0.5: g_0..2 = 0 exactly) every sum that reaches dW1, db1 and
-// the feature tables is the one-output kernel's, term by term in the same order: those gradients are bitwise equal.
-struct StTexField {
-    const float* feats[SG_MAX_LODS];
-    int32_t level[SG_MAX_LODS];
     int num_lods, channels, half_round, hidden, max_level, pos_input;
-    const float *w1, *b1, *w2, *b2;
+    const float *w1, *b1, *w2, *b2;          // [hidden][in_dim], [hidden], [n_out][hidden], [n_out]
 };
 
-static inline int st_tex_entries(int hidden, int in_dim) { return hidden * in_dim + 5 * hidden + 4 + 3; }
+// squared errors a sample leaves behind: its distance error and, with colour outputs, its colour error
+static __host__ __device__ constexpr int st_n_sq(int n_out) { return n_out == 1 ? 1 : 2; }
 
+// Every size of the step, from (hidden, in_dim, n_out), for the scratch sizes, the host body and both kernels.
+//   a workgroup's partial row = the entries of the reduce kernel: dW1 [H][in_dim] at 0, db1 [H] at e_b1, dW2 [n_out][H] at e_w2,
+//   db2 [n_out] at e_b2, the squared-error sums at e_sq and, where there are two of them, their total; `entries` in all,
+//   rows row_stride apart
+//   the dynamic LDS of sdf_train_kernel, as offsets in floats; `floats` = its size
+struct StLayout { int e_b1, e_w2, e_b2, e_sq, entries, row_stride, w1, b1, w2, in, ga, r, g, sq, lev, wm, own, floats; };
+static __host__ __device__ inline StLayout st_layout(int hidden, int in_dim, int n_out) {
+    StLayout s;
+    s.e_b1 = hidden * in_dim;
+    s.e_w2 = s.e_b1 + hidden;
+    s.e_b2 = s.e_w2 + n_out * hidden;
+    s.e_sq = s.e_b2 + n_out;
+    s.entries = s.e_sq + st_n_sq(n_out) + (st_n_sq(n_out) > 1);
+    s.row_stride = (s.entries + 15) / 16 * 16;
+    s.w1 = 0;                                           // [H][in_dim | 1]      odd row stride: the lanes of a group read different rows
+    s.b1 = s.w1 + hidden * (in_dim | 1);                // [H]
+    s.w2 = s.b1 + hidden;                               // [n_out][H]
+    s.in = s.w2 + n_out * hidden;                       // [spb][in_dim]        decoder inputs of the pass
+    s.ga = s.in + ST_GROUPS * in_dim;                   // [spb][H]             d loss / d pre-activation
+    s.r = s.ga + ST_GROUPS * hidden;                    // [spb][H]             relu output (one output: times d loss / d pred)
+    s.g = s.r + ST_GROUPS * hidden;                     // [spb][n_out]         d loss / d y
+    s.sq = s.g + ST_GROUPS * n_out;                     // [spb][n_sq]          squared distance error (, squared colour error)
+    s.lev = s.sq + ST_GROUPS * st_n_sq(n_out);          // [groups][C]          one level's lookup of one sample
+    s.wm = s.lev + ST_GROUPS * ST_GROUP;                // [groups]             its largest corner weight
+    s.own = s.wm + ST_GROUPS;                           // [entries]            this workgroup's partial row
+    s.floats = s.own + s.entries;
+    return s;
+}
+static inline int st_grid(int64_t n, int num_lods) { return (int)min64(ceil_div64(n, ST_GROUPS / num_lods), 1024); }
+static inline int64_t st_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int in_dim, int n_out) {
+    return (int64_t)st_grid(n, num_lods) * st_layout(hidden, in_dim, n_out).row_stride * 4 + sg_round64(n * channels * 4) + n * num_lods * 8;
+}
+
+// Phase 1 for one (sample, level) pair, all 16 lanes of its group together: walk to the cell of sample s on level fld.level[li]
+// (node = -1 outside the cube or in an unoccupied cell), blend feature channel c of its corners (acc; it and wm come in as 0) and
+// return the largest corner weight (wm); lane 0 records the node at node_out.  The blend is an fmaf chain over the corners in
+// corner order from +0, as sdf_eval_point spells it (the other products are by powers of two: exact, fused or not).
+static __device__ __forceinline__ void st_lookup(const StField& fld, const float* __restrict__ coords, const uint8_t* __restrict__ octree,
+                                                 const int32_t* __restrict__ exsum, const int16_t* __restrict__ points,
+                                                 const int32_t* __restrict__ trinkets, int64_t s, int li, int c,
+                                                 int64_t* __restrict__ node_out, float& acc, float& wm) {
+#pragma clang fp contract(off)
+    const int C = fld.channels, L = fld.max_level;
+    const float px = coords[s * 3], py = coords[s * 3 + 1], pz = coords[s * 3 + 2];
+    const bool inside = (fabsf(px) <= 1.0f) && (fabsf(py) <= 1.0f) && (fabsf(pz) <= 1.0f);
+    const float res = (float)(1 << L);
+    const int top = (1 << L) - 1;
+    const int qx = min((int)floorf(res * (0.5f * px + 0.5f)), top);
+    const int qy = min((int)floorf(res * (0.5f * py + 0.5f)), top);
+    const int qz = min((int)floorf(res * (0.5f * pz + 0.5f)), top);
+    const float pos[3] = {px, py, pz};
+    const int lv = fld.level[li];
+    int64_t node = inside ? 0 : -1;
+    for (int l = 0; l < lv && node >= 0; ++l) {                           // (spc_query_kernel's walk)
+        const int sh = L - 1 - l, cs = (((qx >> sh) & 1) << 2) | (((qy >> sh) & 1) << 1) | ((qz >> sh) & 1);
+        const uint32_t bits = octree[node];                               // both loads of a level go out together: one round
+        const int64_t first = (int64_t)exsum[node];                       // trip per level, not two
+        const int64_t child = first + __popc(bits & ((2u << cs) - 1u));
+        node = ((bits >> cs) & 1u) ? child : -1;
+    }
+    if (c == 0) *node_out = node;                                         // (now: the node need not live through the blend)
+    if (node >= 0) {
+        float w[8];
+        sg_coeffs(pos, points + node * 3, lv, w);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wm = fmaxf(wm, fabsf(w[j]));
+        const int32_t* tr = trinkets + node * 8;
+        const float* f = fld.feats[li];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float fv = f[(int64_t)tr[j] * C + c];
+            if (fld.half_round) fv = __half2float(__float2half_rn(fv));
+            acc = __builtin_fmaf(fv, w[j], acc);
+        }
+        if (fld.half_round) acc = __half2float(__float2half_rn(acc));
+    }
+}
+
+template <int NOUT>
 __global__ void __launch_bounds__(ST_GROUP * ST_GROUPS)
-sdf_tex_train_kernel(const float* __restrict__ coords, const float* __restrict__ gts, const float* __restrict__ rgb_gts, int64_t n,
-                     const uint8_t* __restrict__ octree, const int32_t* __restrict__ exsum, const int16_t* __restrict__ points,
-                     const int32_t* __restrict__ trinkets, StTexField fld, float inv_batch,
-                     float* __restrict__ partials /* [grid][row] */, int row_stride, float* __restrict__ dfeat /* [n][channels] */,
-                     int64_t* __restrict__ chain /* [n][num_lods] */, SgHeader* __restrict__ hdr) {
-    extern __shared__ float s_stx[];
+sdf_train_kernel(const float* __restrict__ coords, const float* __restrict__ gts, const float* __restrict__ rgb_gts /* NOUT == 4 */,
+                 int64_t n, const uint8_t* __restrict__ octree, const int32_t* __restrict__ exsum, const int16_t* __restrict__ points,
+                 const int32_t* __restrict__ trinkets, StField fld, float inv_batch, float* __restrict__ partials /* [grid][row] */,
+                 float* __restrict__ dfeat /* [n][channels] */, int64_t* __restrict__ chain /* [n][num_lods] */, SgHeader* __restrict__ hdr) {
+    // Every fused multiply-add is written as one, here and in st_lookup, and the compiler's own contraction is off: left to it,
+    // one source fused the corner blend and the colour error in one way as a kernel of its own and in another as an instantiation
+#pragma clang fp contract(off)
+    static_assert(NOUT == 1 || NOUT == 4, "one output (distance) or four (colour, distance)");
+    constexpr int NSQ = st_n_sq(NOUT);
+    extern __shared__ float s_st[];
     const int C = fld.channels, H = fld.hidden, NL = fld.num_lods;
     const int fo = fld.pos_input ? 3 : 0;               // first feature column of the decoder input
     const int in_dim = fo + C;
-    const int in_pad = in_dim | 1;                      // odd row stride: the lanes of a group read different rows
+    const int in_pad = in_dim | 1;
     const int spb = ST_GROUPS / NL;                     // samples per workgroup pass: one lane group per (sample, level)
-    float* s_w1 = s_stx;                                // [H][in_pad]
-    float* s_b1 = s_w1 + H * in_pad;                    // [H]
-    float* s_w2 = s_b1 + H;                             // [4][H]
-    float* s_in = s_w2 + 4 * H;                         // [spb][in_dim]        decoder inputs of the pass
-    float* s_ga = s_in + ST_GROUPS * in_dim;            // [spb][H]             d loss / d pre-activation
-    float* s_r = s_ga + ST_GROUPS * H;                  // [spb][H]             relu output (for d W2)
-    float* s_g = s_r + ST_GROUPS * H;                   // [spb][4]             d loss / d y
-    float* s_sq = s_g + ST_GROUPS * 4;                  // [spb][2]             squared distance error, squared colour error
-    float* s_lev = s_sq + ST_GROUPS * 2;                // [groups][C]          one level's lookup of one sample
-    float* s_wm = s_lev + ST_GROUPS * ST_GROUP;         // [groups]             its largest corner weight
+    const StLayout lay = st_layout(H, in_dim, NOUT);
+    float *s_w1 = s_st + lay.w1, *s_b1 = s_st + lay.b1, *s_w2 = s_st + lay.w2, *s_in = s_st + lay.in, *s_ga = s_st + lay.ga;
+    float *s_r = s_st + lay.r, *s_g = s_st + lay.g, *s_sq = s_st + lay.sq, *s_lev = s_st + lay.lev, *s_wm = s_st + lay.wm;
+    float* s_own = s_st + lay.own;                      // every entry of the partial row has one owner
     for (int e = threadIdx.x; e < H * in_dim; e += blockDim.x) s_w1[(e / in_dim) * in_pad + e % in_dim] = fld.w1[e];
     for (int e = threadIdx.x; e < H; e += blockDim.x) s_b1[e] = fld.b1[e];
-    for (int e = threadIdx.x; e < 4 * H; e += blockDim.x) s_w2[e] = fld.w2[e];
+    for (int e = threadIdx.x; e < NOUT * H; e += blockDim.x) s_w2[e] = fld.w2[e];
+    for (int e = threadIdx.x; e < lay.entries; e += blockDim.x) s_own[e] = 0.0f;
     const int c = threadIdx.x & (ST_GROUP - 1);
     const int grp = threadIdx.x / ST_GROUP;
-    const int L = fld.max_level;
-    const float b2[4] = {fld.b2[0], fld.b2[1], fld.b2[2], fld.b2[3]};
-    // partial sums of this workgroup: d W1 [H][in_dim], d b1 [H], d W2 [4][H], d b2 [4], distance / colour / total squared error -
-    // in that order; every entry has one owner
-    const int o_b1 = H * in_dim, o_w2 = o_b1 + H, o_b2 = o_w2 + 4 * H, o_sq = o_b2 + 4;
-    const int n_entries = o_sq + 3;
-    float* s_own = s_wm + ST_GROUPS;                    // [n_entries]
-    for (int e = threadIdx.x; e < n_entries; e += blockDim.x) s_own[e] = 0.0f;
+    float b2[NOUT];
+    for (int o = 0; o < NOUT; ++o) b2[o] = fld.b2[o];
     uint32_t mbits = 0;
     const int my_si = grp / NL, my_li = grp - my_si * NL;                 // phase 1: this group's (sample of the pass, level)
     __syncthreads();
     for (int64_t base = (int64_t)blockIdx.x * spb; base < n; base += (int64_t)gridDim.x * spb) {
-        // ---- phase 1: sdf_train_kernel's, statement for statement
+        // ---- phase 1: every (sample, level) pair on its own lane group: six groups walking at once cost the deepest one's time
         {
             const int64_t s = base + my_si;
             float acc = 0.0f, wm = 0.0f;
-            if (my_si < spb && s < n) {
-                const float px = coords[s * 3], py = coords[s * 3 + 1], pz = coords[s * 3 + 2];
-                const bool inside = (fabsf(px) <= 1.0f) && (fabsf(py) <= 1.0f) && (fabsf(pz) <= 1.0f);
-                const float res = (float)(1 << L);
-                const int top = (1 << L) - 1;
-                const int qx = min((int)floorf(res * (0.5f * px + 0.5f)), top);
-                const int qy = min((int)floorf(res * (0.5f * py + 0.5f)), top);
-                const int qz = min((int)floorf(res * (0.5f * pz + 0.5f)), top);
-                const float pos[3] = {px, py, pz};
-                const int lv = fld.level[my_li];
-                int64_t node = inside ? 0 : -1;
-                for (int l = 0; l < lv && node >= 0; ++l) {               // (spc_query_kernel's walk)
-                    const int cs = st_child_slot(qx, qy, qz, L - 1 - l);
-                    const uint32_t bits = octree[node];                   // both loads of a level go out together: one round
-                    const int64_t first = (int64_t)exsum[node];           // trip per level, not two
-                    const int64_t child = first + __popc(bits & ((2u << cs) - 1u));
-                    node = ((bits >> cs) & 1u) ? child : -1;
-                }
-                if (c == 0) chain[s * NL + my_li] = node;
-                if (node >= 0) {
-                    float w[8];
-                    sg_coeffs(pos, points + node * 3, lv, w);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) wm = fmaxf(wm, fabsf(w[j]));
-                    const int32_t* tr = trinkets + node * 8;
-                    const float* f = fld.feats[my_li];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        float fv = f[(int64_t)tr[j] * C + c];
-                        if (fld.half_round) fv = __half2float(__float2half_rn(fv));
-                        acc += fv * w[j];
-                    }
-                    if (fld.half_round) acc = __half2float(__float2half_rn(acc));
-                }
-            }
+            if (my_si < spb && s < n) st_lookup(fld, coords, octree, exsum, points, trinkets, s, my_li, c, chain + s * NL + my_li, acc, wm);
             s_lev[grp * ST_GROUP + c] = acc;
             if (c == 0) s_wm[grp] = wm;
         }
@@ -1160,54 +936,56 @@ sdf_tex_train_kernel(const float* __restrict__ coords, const float* __restrict__
         }
         __builtin_amdgcn_wave_barrier();                 // a group's lanes are in one wave: LDS order suffices
         if (live) {
-            // decoder forward: in = [position, features] (neural_sdf_tex.py: embedded position first) or the features alone
-            float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
+            // decoder forward: in = [position, features] (the modules put the embedded position first) or the features alone
+            float out[NOUT] = {};
             for (int hh = c; hh < H; hh += ST_GROUP) {
                 const float* wr = s_w1 + hh * in_pad;
                 float a = s_b1[hh];
                 for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
                 const float r = fmaxf(a, 0.0f);
-                o0 = __builtin_fmaf(s_w2[hh], r, o0);
-                o1 = __builtin_fmaf(s_w2[H + hh], r, o1);
-                o2 = __builtin_fmaf(s_w2[2 * H + hh], r, o2);
-                o3 = __builtin_fmaf(s_w2[3 * H + hh], r, o3);
+                for (int o = 0; o < NOUT; ++o) out[o] = __builtin_fmaf(s_w2[o * H + hh], r, out[o]);
                 ga[hh] = a > 0.0f ? 1.0f : 0.0f;        // the relu mask; finished below, once d loss / d y is known
                 gr[hh] = r;
             }
 #pragma unroll
-            for (int d = ST_GROUP / 2; d >= 1; d >>= 1) {
-                o0 += __shfl_xor(o0, d, ST_GROUP);
-                o1 += __shfl_xor(o1, d, ST_GROUP);
-                o2 += __shfl_xor(o2, d, ST_GROUP);
-                o3 += __shfl_xor(o3, d, ST_GROUP);
+            for (int d = ST_GROUP / 2; d >= 1; d >>= 1)
+                for (int o = 0; o < NOUT; ++o) out[o] += __shfl_xor(out[o], d, ST_GROUP);
+            // ---- the loss head, the one part that differs by field: g = d loss / d y, sq = the sample's squared errors.  The
+            //      distance is the last output; the colours before it go through a sigmoid
+            float g[NOUT], sq[NSQ];
+            const float dd = (out[NOUT - 1] + b2[NOUT - 1]) - gts[s];
+            g[NOUT - 1] = 2.0f * dd * inv_batch;         // d [sum (sdf - gt)^2 / B] / d sdf
+            sq[0] = dd * dd;
+            if constexpr (NOUT == 4) {
+                float d[3];
+                for (int o = 0; o < 3; ++o) {
+                    const float co = 1.0f / (1.0f + expf(-(out[o] + b2[o])));
+                    d[o] = co - rgb_gts[s * 3 + o];
+                    g[o] = 2.0f * d[o] * (co * (1.0f - co)) * inv_batch;      // d loss / d y_o through the sigmoid
+                }
+                sq[1] = __builtin_fmaf(d[1], d[1], d[0] * d[0]) + d[2] * d[2];
             }
-            const float c0 = 1.0f / (1.0f + expf(-(o0 + b2[0])));
-            const float c1 = 1.0f / (1.0f + expf(-(o1 + b2[1])));
-            const float c2 = 1.0f / (1.0f + expf(-(o2 + b2[2])));
-            const float d0 = c0 - rgb_gts[s * 3], d1 = c1 - rgb_gts[s * 3 + 1], d2 = c2 - rgb_gts[s * 3 + 2];
-            const float d3 = (o3 + b2[3]) - gts[s];
-            const float g0 = 2.0f * d0 * (c0 * (1.0f - c0)) * inv_batch;      // d loss / d y_o through the sigmoid
-            const float g1 = 2.0f * d1 * (c1 * (1.0f - c1)) * inv_batch;
-            const float g2 = 2.0f * d2 * (c2 * (1.0f - c2)) * inv_batch;
-            const float g3 = 2.0f * d3 * inv_batch;                           // d [sum (sdf - gt)^2 / B] / d sdf
+            // ---- end of the loss head
             for (int hh = c; hh < H; hh += ST_GROUP) {
-                float t = __builtin_fmaf(s_w2[hh], g0, 0.0f);
-                t = __builtin_fmaf(s_w2[H + hh], g1, t);
-                t = __builtin_fmaf(s_w2[2 * H + hh], g2, t);
-                t = __builtin_fmaf(s_w2[3 * H + hh], g3, t);
+                // rounding: one output forms the plain product; four form an fmaf chain from +0, which differs from it where the
+                // first product is -0 - each keeps its own
+                float t = NOUT == 1 ? s_w2[hh] * g[0] : __builtin_fmaf(s_w2[hh], g[0], 0.0f);
+                for (int o = 1; o < NOUT; ++o) t = __builtin_fmaf(s_w2[o * H + hh], g[o], t);
+                // the relu's backward SELECTS: a unit that is off passes 0 on, also for a non-finite g, where a product with the
+                // mask would be 0 * inf = NaN
                 ga[hh] = ga[hh] != 0.0f ? t : 0.0f;
+                if constexpr (NOUT == 1) gr[hh] *= g[0];                      // rounding: see d W2 in phase 3
             }
             if (c == 0) {
-                s_g[grp * 4] = g0; s_g[grp * 4 + 1] = g1; s_g[grp * 4 + 2] = g2; s_g[grp * 4 + 3] = g3;
-                s_sq[grp * 2] = d3 * d3;
-                s_sq[grp * 2 + 1] = (d0 * d0 + d1 * d1) + d2 * d2;
+                for (int o = 0; o < NOUT; ++o) s_g[grp * NOUT + o] = g[o];
+                for (int k = 0; k < NSQ; ++k) s_sq[grp * NSQ + k] = sq[k];
             }
         } else if (grp < spb) {
             for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = 0.0f; gr[hh] = 0.0f; }
             if (c < fo) gin[c] = 0.0f;
             gin[fo + c] = 0.0f;
-            if (c < 4) s_g[grp * 4 + c] = 0.0f;
-            if (c < 2) s_sq[grp * 2 + c] = 0.0f;
+            if (c < NOUT) s_g[grp * NOUT + c] = 0.0f;
+            if (c < NSQ) s_sq[grp * NSQ + c] = 0.0f;
         }
         __builtin_amdgcn_wave_barrier();
         if (live) {
@@ -1221,67 +999,132 @@ sdf_tex_train_kernel(const float* __restrict__ coords, const float* __restrict__
         }
         __syncthreads();
         // ---- phase 3: weight gradients of this pass: the thread that owns an entry adds the samples up in order
-        for (int e = threadIdx.x; e < n_entries; e += blockDim.x) {
+        for (int e = threadIdx.x; e < lay.entries; e += blockDim.x) {
             float acc = 0.0f;
-            if (e < o_b1) {
+            if (e < lay.e_b1) {
                 const int hh = e / in_dim, i = e - hh * in_dim;
                 for (int q = 0; q < spb; ++q) acc = __builtin_fmaf(s_ga[q * H + hh], s_in[q * in_dim + i], acc);
-            } else if (e < o_w2) {
-                const int hh = e - o_b1;
+            } else if (e < lay.e_w2) {
+                const int hh = e - lay.e_b1;
                 for (int q = 0; q < spb; ++q) acc += s_ga[q * H + hh];
-            } else if (e < o_b2) {
-                const int o = (e - o_w2) / H, hh = (e - o_w2) - o * H;
-                for (int q = 0; q < spb; ++q) acc = __builtin_fmaf(s_g[q * 4 + o], s_r[q * H + hh], acc);
-            } else if (e < o_sq) {
-                for (int q = 0; q < spb; ++q) acc += s_g[q * 4 + (e - o_b2)];
-            } else if (e < o_sq + 2) {
-                for (int q = 0; q < spb; ++q) acc += s_sq[q * 2 + (e - o_sq)];
-            } else {
+            } else if (e < lay.e_b2) {
+                // rounding: d W2 of one output adds the products r * g that phase 2 stored (a rounded product, then a plain add);
+                // four outputs keep r and fuse, fmaf(g, r, acc).  The two differ in the last bit, and each keeps its own.
+                const int o = NOUT == 1 ? 0 : (e - lay.e_w2) / H, hh = (e - lay.e_w2) - o * H;
+                for (int q = 0; q < spb; ++q)
+                    acc = NOUT == 1 ? acc + s_r[q * H + hh] : __builtin_fmaf(s_g[q * NOUT + o], s_r[q * H + hh], acc);
+            } else if (e < lay.e_sq) {
+                for (int q = 0; q < spb; ++q) acc += s_g[q * NOUT + (e - lay.e_b2)];
+            } else if (e < lay.e_sq + NSQ) {
+                for (int q = 0; q < spb; ++q) acc += s_sq[q * NSQ + (e - lay.e_sq)];
+            } else if constexpr (NSQ == 2) {                                  // the total: colour + distance, in that order
                 for (int q = 0; q < spb; ++q) acc += s_sq[q * 2 + 1] + s_sq[q * 2];
             }
             s_own[e] += acc;
         }
         __syncthreads();
     }
-    for (int e = threadIdx.x; e < n_entries; e += blockDim.x) partials[(int64_t)blockIdx.x * row_stride + e] = s_own[e];
+    for (int e = threadIdx.x; e < lay.entries; e += blockDim.x) partials[(int64_t)blockIdx.x * lay.row_stride + e] = s_own[e];
     mbits = sg_wave_umax(mbits);
     if ((threadIdx.x & 63) == 0 && mbits > __atomic_load_n(&hdr->absmax_bits, __ATOMIC_RELAXED)) atomicMax(&hdr->absmax_bits, mbits);
 }
 
 __global__ void __launch_bounds__(256)
-sdf_tex_train_reduce_kernel(const float* __restrict__ partials, int rows, int row_stride, int H, int in_dim, float* __restrict__ gw1,
-                            float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2, float* __restrict__ loss,
-                            float inv_batch) {
+sdf_train_reduce_kernel(const float* __restrict__ partials, int rows, int H, int in_dim, int n_out,
+                        float* __restrict__ gw1, float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2,
+                        float* __restrict__ loss, float inv_batch) {
     // 16 lanes per entry: lane r adds rows r, r + 16, ... in order, then a fixed butterfly over the 16 lanes
-    const int o_b1 = H * in_dim, o_w2 = o_b1 + H, o_b2 = o_w2 + 4 * H, o_sq = o_b2 + 4;
-    const int n_entries = o_sq + 3;
+    const StLayout lay = st_layout(H, in_dim, n_out);
     const int r0 = threadIdx.x & 15;
-    for (int e = blockIdx.x * 16 + (threadIdx.x >> 4); e < n_entries + 15; e += gridDim.x * 16) {      // (whole groups stay together)
-        const bool in = e < n_entries;
+    for (int e = blockIdx.x * 16 + (threadIdx.x >> 4); e < lay.entries + 15; e += gridDim.x * 16) {          // (whole groups stay together)
+        const bool in = e < lay.entries;
         float acc = 0.0f;
         if (in)
-            for (int r = r0; r < rows; r += 16) acc += partials[(int64_t)r * row_stride + e];
+            for (int r = r0; r < rows; r += 16) acc += partials[(int64_t)r * lay.row_stride + e];
 #pragma unroll
         for (int d = 8; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 16);
         if (!in || r0 != 0) continue;
-        if (e < o_b1) gw1[e] += acc;
-        else if (e < o_w2) gb1[e - o_b1] += acc;
-        else if (e < o_b2) gw2[e - o_w2] += acc;
-        else if (e < o_sq) gb2[e - o_b2] += acc;
-        else if (e == o_sq) loss[1] = acc;                                  // un-normalised: what the tracker adds up as l2_loss
-        else if (e == o_sq + 1) loss[2] = acc;                              // ... as rgb_loss
-        else loss[0] = acc * inv_batch;
+        if (e < lay.e_b1) gw1[e] += acc;
+        else if (e < lay.e_w2) gb1[e - lay.e_b1] += acc;
+        else if (e < lay.e_b2) gw2[e - lay.e_w2] += acc;
+        else if (e < lay.e_sq) gb2[e - lay.e_b2] += acc;
+        else if (e == lay.entries - 1) loss[0] = acc * inv_batch;                 // the last entry is the whole squared error
+        else loss[1 + (e - lay.e_sq)] = acc;          // un-normalised: what the tracker adds up as l2_loss, then as rgb_loss
     }
 }
 
-static inline int st_tex_row_stride(int hidden, int in_dim) { return (st_tex_entries(hidden, in_dim) + 15) / 16 * 16; }
+// The body of both entry points, after their own argument checks; who = the entry point, for its error messages
+template <int NOUT>
+static int st_step(const char* who, const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
+                   const int32_t* exsum, const int16_t* points, const int32_t* trinkets, const float* const* feats,
+                   const int32_t* levels, const int64_t* rows, int num_lods, int channels, int half_round, int pos_input,
+                   const float* w1, const float* b1, const float* w2, const float* b2, int hidden, float* const* grad_feats,
+                   float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, float* loss, void* scratch, void* workspace,
+                   int64_t workspace_bytes, hipStream_t s) {
+    StField fld;
+    SgLods ml;
+    if (sg_fill(ml, levels, rows, num_lods) != 0) return wisp_fail(WISP_ERR_INVALID, who, "bad level or row count");
+    for (int l = 0; l < num_lods; ++l) {
+        if (!(feats[l] && grad_feats[l] && (l == 0 || levels[l] > levels[l - 1]))) return wisp_fail(WISP_ERR_INVALID, who, "bad level list");
+        fld.feats[l] = feats[l]; fld.level[l] = levels[l]; ml.grad[l] = grad_feats[l];
+    }
+    fld.num_lods = num_lods; fld.channels = channels; fld.half_round = half_round; fld.hidden = hidden;
+    fld.max_level = levels[num_lods - 1]; fld.pos_input = pos_input;
+    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
+    const SgPlan pl = sg_plan(ml.base[num_lods], channels, 0);
+    if (workspace_bytes < pl.bytes) return wisp_fail(WISP_ERR_INVALID, who, "workspace too small (wisp_spc_bwd_workspace_bytes)");
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    SgHeader* hdr = reinterpret_cast<SgHeader*>(ws);
+    const int in_dim = (pos_input ? 3 : 0) + channels;
+    const int grid = st_grid(n, num_lods);
+    const StLayout lay = st_layout(hidden, in_dim, NOUT);
+    float* partials = static_cast<float*>(scratch);
+    float* dfeat = partials + (size_t)grid * lay.row_stride;
+    int64_t* chain = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(dfeat) + sg_round64(n * channels * 4));
+    const size_t lds = (size_t)lay.floats * sizeof(float);
+    const float inv_batch = 1.0f / (float)n;
+    if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, who, "hipMemsetAsync failed");
+    if (const hipError_t e = WISP_ALLOW_LDS(sdf_train_kernel<NOUT>, lds)) return wisp_fail(WISP_ERR_LAUNCH, who, hipGetErrorString(e));
+    hipLaunchKernelGGL(sdf_train_kernel<NOUT>, dim3(grid), dim3(ST_GROUP * ST_GROUPS), lds, s, coords, gts, rgb_gts, n, octree, exsum,
+                       points, trinkets, fld, inv_batch, partials, dfeat, chain, hdr);
+    hipLaunchKernelGGL(sdf_train_reduce_kernel, dim3((lay.entries + 15) / 16), dim3(256), 0, s, partials, grid, hidden, in_dim, NOUT,
+                       grad_w1, grad_b1, grad_w2, grad_b2, loss, inv_batch);
+    // the corner sums: the magnitude bound is in the header already (sdf_train_kernel), so only scatter + row pass
+    const SgCall c{coords, chain, 1, num_lods, 1, points, trinkets, dfeat, n, num_lods, channels, 1, channels};
+    sg_scatter(c, ml, pl, ws, s, true);                                   // (without its memset nothing in it can fail)
+    sg_finalize(c, ml, pl, ws, s);
+    if (const hipError_t e = hipGetLastError()) return wisp_fail(WISP_ERR_LAUNCH, who, hipGetErrorString(e));
+    return WISP_OK;
+}
+
+extern "C" int64_t wisp_sdf_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden) {
+    if (n < 0 || num_lods < 1 || num_lods > SG_MAX_LODS || channels < 1 || hidden < 1) return -1;
+    return st_scratch_bytes(n, num_lods, channels, hidden, 3 + channels, 1);
+}
+
+extern "C" int wisp_sdf_train_step(const float* coords, const float* gts, int64_t n, const uint8_t* octree, const int32_t* exsum,
+                                   const int16_t* points, const int32_t* trinkets, const float* const* feats,
+                                   const int32_t* levels, const int64_t* rows, int num_lods, int channels, int half_round,
+                                   const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
+                                   float* const* grad_feats, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
+                                   float* loss, void* scratch, int64_t scratch_bytes, void* workspace, int64_t workspace_bytes,
+                                   wisp_stream_t stream) {
+    WISP_REQUIRE(n >= 1 && num_lods >= 1 && num_lods <= SG_MAX_LODS, "bad sizes");
+    WISP_REQUIRE(channels == ST_GROUP, "the fused SDF step is built for 16 feature channels (nglod_octree.yaml)");
+    WISP_REQUIRE(hidden >= 1 && hidden <= ST_MAX_HIDDEN, "hidden width out of range");
+    WISP_REQUIRE(coords && gts && octree && exsum && points && trinkets && feats && levels && rows && w1 && b1 && w2 && b2 &&
+                 grad_feats && grad_w1 && grad_b1 && grad_w2 && grad_b2 && loss && scratch && workspace, "null pointer");
+    WISP_REQUIRE(scratch_bytes >= wisp_sdf_train_scratch_bytes(n, num_lods, channels, hidden), "scratch too small (wisp_sdf_train_scratch_bytes)");
+    return st_step<1>(__func__, coords, gts, nullptr, n, octree, exsum, points, trinkets, feats, levels, rows, num_lods, channels,
+                      half_round, 1, w1, b1, w2, b2, hidden, grad_feats, grad_w1, grad_b1, grad_w2, grad_b2, loss, scratch, workspace,
+                      workspace_bytes, (hipStream_t)stream);
+}
 
 extern "C" int64_t wisp_sdf_tex_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int pos_input) {
     if (n < 0 || num_lods < 1 || num_lods > SG_MAX_LODS || channels != ST_GROUP || hidden < 1 || hidden > ST_MAX_HIDDEN ||
         (pos_input != 0 && pos_input != 1))
         return -1;
-    return (int64_t)st_grid(n, num_lods) * st_tex_row_stride(hidden, (pos_input ? 3 : 0) + channels) * 4 + sg_round64(n * channels * 4) +
-           n * num_lods * 8;
+    return st_scratch_bytes(n, num_lods, channels, hidden, (pos_input ? 3 : 0) + channels, 4);
 }
 
 extern "C" int wisp_sdf_tex_train_step(const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
@@ -1299,50 +1142,7 @@ extern "C" int wisp_sdf_tex_train_step(const float* coords, const float* gts, co
                  b2 && grad_feats && grad_w1 && grad_b1 && grad_w2 && grad_b2 && loss && scratch && workspace, "null pointer");
     WISP_REQUIRE(scratch_bytes >= wisp_sdf_tex_train_scratch_bytes(n, num_lods, channels, hidden, pos_input),
                  "scratch too small (wisp_sdf_tex_train_scratch_bytes)");
-    StTexField fld;
-    SgLods ml;
-    WISP_REQUIRE(sg_fill(ml, levels, rows, num_lods) == 0, "bad level or row count");
-    for (int l = 0; l < num_lods; ++l) {
-        WISP_REQUIRE(feats[l] && grad_feats[l] && (l == 0 || levels[l] > levels[l - 1]), "bad level list");
-        fld.feats[l] = feats[l]; fld.level[l] = levels[l]; ml.grad[l] = grad_feats[l];
-    }
-    fld.num_lods = num_lods; fld.channels = channels; fld.half_round = half_round; fld.hidden = hidden;
-    fld.max_level = levels[num_lods - 1]; fld.pos_input = pos_input;
-    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
-    const SgPlan pl = sg_plan(ml.base[num_lods], channels, 0);
-    WISP_REQUIRE(workspace_bytes >= pl.bytes, "workspace too small (wisp_spc_bwd_workspace_bytes)");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    SgHeader* hdr = reinterpret_cast<SgHeader*>(ws);
-    const int in_dim = (pos_input ? 3 : 0) + channels;
-    const int grid = st_grid(n, num_lods), row_stride = st_tex_row_stride(hidden, in_dim), n_entries = st_tex_entries(hidden, in_dim);
-    float* partials = static_cast<float*>(scratch);
-    float* dfeat = partials + (size_t)grid * row_stride;
-    int64_t* chain = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(dfeat) + sg_round64(n * channels * 4));
-    const size_t lds = ((size_t)hidden * (in_dim | 1) + 5 * hidden + (size_t)ST_GROUPS * (in_dim + 2 * hidden + 4 + 2 + ST_GROUP + 1) +
-                        (size_t)n_entries) * 4;
-    const float inv_batch = 1.0f / (float)n;
-    if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, __func__, "hipMemsetAsync failed");
-    if (const hipError_t e = WISP_ALLOW_LDS(sdf_tex_train_kernel, lds)) return wisp_fail(WISP_ERR_LAUNCH, __func__, hipGetErrorString(e));
-    hipLaunchKernelGGL(sdf_tex_train_kernel, dim3(grid), dim3(ST_GROUP * ST_GROUPS), lds, s, coords, gts, rgb_gts, n, octree, exsum,
-                       points, trinkets, fld, inv_batch, partials, row_stride, dfeat, chain, hdr);
-    hipLaunchKernelGGL(sdf_tex_train_reduce_kernel, dim3((n_entries + 15) / 16), dim3(256), 0, s, partials, grid, row_stride, hidden,
-                       in_dim, grad_w1, grad_b1, grad_w2, grad_b2, loss, inv_batch);
-    // the corner sums: the magnitude bound is in the header already (sdf_tex_train_kernel), so only scatter + row pass
-    SgCall c{coords, chain, 1, num_lods, 1, points, trinkets, dfeat, n, num_lods, channels, 1, channels};
-    uint8_t* flags = sg_use_flags(c, pl) ? ws + pl.off_flags : nullptr;
-    long long* acc = reinterpret_cast<long long*>(ws + pl.off_acc);
-    const int clog = sg_clog(n);
-    const int split = sg_split_lods(c);
-    hipLaunchKernelGGL((spc_grad_scatter_wide_kernel<int64_t>),
-                       dim3((unsigned)min64(ceil_div64(n * (split ? num_lods : 1), 256 / channels), 16384)), dim3(256), 0, s, coords, chain,
-                       (int64_t)num_lods, 1, points, trinkets, ml, dfeat, n, num_lods, channels, 1, clog, pl.stride, channels, hdr, flags,
-                       acc, split);
-    int lpr = 1;
-    while (lpr < channels && lpr < 64) lpr <<= 1;
-    if (pl.total_rows > 0)
-        hipLaunchKernelGGL(spc_grad_finalize_kernel, dim3((unsigned)min64(ceil_div64(pl.total_rows, 256 / lpr), 8192)), dim3(256), 0, s, ml,
-                           num_lods, channels, pl.stride, lpr, clog, hdr, flags, acc);
-    WISP_CHECK_LAUNCH();
-    return WISP_OK;
+    return st_step<4>(__func__, coords, gts, rgb_gts, n, octree, exsum, points, trinkets, feats, levels, rows, num_lods, channels,
+                      half_round, pos_input, w1, b1, w2, b2, hidden, grad_feats, grad_w1, grad_b1, grad_w2, grad_b2, loss, scratch,
+                      workspace, workspace_bytes, (hipStream_t)stream);
 }

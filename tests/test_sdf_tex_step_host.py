@@ -85,13 +85,15 @@ def test_the_two_kernels_have_no_scratch_and_256_thread_workgroups():
     meta = kernel_meta.kernels(LIB)
     names = kernel_meta.demangled(list(meta))
     kern = {names[k]: v for k, v in meta.items()}
-    for part in ("sdf_tex_train_kernel", "sdf_tex_train_reduce_kernel"):
-        hits = {n: v for n, v in kern.items() if part in n}
+    # both instantiations of the one train kernel (one output, four outputs) and the one reduce kernel both steps share
+    for part in ("void sdf_train_kernel<1>(", "void sdf_train_kernel<4>(", "sdf_train_reduce_kernel("):
+        hits = {n: v for n, v in kern.items() if n.startswith(part)}
         assert len(hits) == 1, (part, list(hits))
         for name, v in hits.items():
             assert v["scratch"] == 0 and v["wg"] == 256, (name, v)
-    # dynamic LDS only (sized per call, raised past the 64 KB default through WISP_ALLOW_LDS as the one-output kernel's is)
-    assert next(v for n, v in kern.items() if "sdf_tex_train_kernel" in n)["lds"] == 0
+            # dynamic LDS only (sized per call, raised past the 64 KB default through WISP_ALLOW_LDS)
+            assert "reduce" in part or v["lds"] == 0, (name, v)
+    assert not [n for n in kern if "sdf_tex_train" in n or n.startswith("sdf_train_kernel(")], "a per-field twin of the kernel"
 
 
 # ------------------------------------------------------------------------------------------------ 3. step() arguments
