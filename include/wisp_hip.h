@@ -43,7 +43,8 @@ const char* wisp_last_error(void);
  * wisp_nerf_mlp_build_operand_image, wisp_nerf_mlp_fwd_rays_img, wisp_nerf_mlp_bwd_rays_img, wisp_hash_sdf_train_step,
  * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_nerf_query, wisp_composite_loss_partials, wisp_loss_sum,
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
- * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim, wisp_triplane_sdf_query,
+ * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -605,8 +606,52 @@ int wisp_hash_sdf_trace_step_fused(int64_t num_packs, int first, const float* nu
                                    const float* w2, const float* b2, int hidden, float scale, int32_t* any_active,
                                    wisp_stream_t stream);
 
+/* The same three evaluations for a NeuralSDF over a TriplanarGrid (nglod_triplanar.yaml; csrc/triplane_sdf_eval.hip): what
+ * NeuralSDF.sdf computes over the grid ops - TriplanarGrid.interpolate (wisp/models/grids/triplanar_grid.py:97-146: per level
+ * TriplanarFeatureVolume.forward, :205-233, three bilinear F.grid_sample lookups with align_corners=True and reflection padding
+ * stacked as [x | y | z], then 'cat' or 'sum' over the levels 0..lod_idx), then [position, features] -> Linear -> relu -> Linear
+ * (wisp/models/nefs/neural_sdf.py:120-155).  The triplanar field:
+ *   planes            HOST array of num_lods * 3 device pointers (x, y, z of level 0, then level 1, ...), each f32
+ *                     [feature_dim, sizes[l], sizes[l]] in torch's parameter layout, exactly as wisp_triplane_fwd takes them
+ *   sizes             HOST int32 [num_lods], every one >= 1
+ *   num_lods          the number of levels evaluated (lod_idx + 1), 1..16;  feature_dim >= 1 is PER PLANE
+ *   multiscale        0 = 'cat' (K = num_lods * 3 * feature_dim feature columns), 1 = 'sum' (K = 3 * feature_dim);  K <= 48
+ *   w1 f32 [hidden, 3 + K] in nn.Linear layout, b1 [hidden], w2 [hidden], b2 [1];  1 <= hidden <= 256
+ * Source coordinates, corner weights and the dropped out-of-plane corners are those of wisp_triplane_fwd (coordinates outside
+ * the cube are reflected); here every rounding is fixed (products, then an fma chain over the corners 00, 01, 10, 11; 'sum'
+ * adds the levels in level order), where wisp_triplane_fwd leaves the contraction to the compiler: the two agree to rounding.  A
+ * shape outside these limits, a null pointer, or a decoder that does not fit 64 KB of LDS returns WISP_ERR_INVALID before any
+ * launch.
+ *
+ * wisp_triplane_sdf_query: coords f32 [n,3] -> out f32 [n,1]; gts / counts as for wisp_sdf_query (compute_sdf_iou,
+ * wisp/ops/sdf/metrics.py:12-29, without the read-back per batch of wisp/trainers/sdf_trainer.py:156-190); out may then be
+ * NULL. */
+int wisp_triplane_sdf_query(const float* coords, int64_t n, const float* const* planes, const int32_t* sizes, int num_lods,
+                            int feature_dim, int multiscale, const float* w1, const float* b1, const float* w2, const float* b2,
+                            int hidden, float* out, const float* gts, int64_t* counts, wisp_stream_t stream);
+
+/* Central-difference gradient of that field in one launch (replaces finitediff_gradient,
+ * wisp/ops/differential/gradients.py:29-45: six field queries): grad[i, a] = (f(x + eps e_a) - f(x - eps e_a)) / (2 eps),
+ * positions and difference in fp32, every value bit for bit what wisp_triplane_sdf_query returns at that position.  grad f32
+ * [n,3]. */
+int wisp_triplane_sdf_fd_gradient(const float* coords, int64_t n, const float* const* planes, const int32_t* sizes, int num_lods,
+                                  int feature_dim, int multiscale, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, int hidden, float eps, float* grad, wisp_stream_t stream);
+
+/* One marching iteration of PackedSDFTracer.trace (wisp/tracers/packed_sdf_tracer.py:118-146) INCLUDING the field query of
+ * that field: everything wisp_sphere_trace_step does, then dist[p] = (decoder(x[p]) + b2) * scale for the packs still marching,
+ * bit for bit wisp_triplane_sdf_query's value at x[p] times scale (first != 0: only the query, for the start positions).  State
+ * arrays and any_active as for wisp_sdf_trace_step_fused. */
+int wisp_triplane_sdf_trace_step_fused(int64_t num_packs, int first, const float* nug_o, const float* nug_d,
+                                       const float* nug_depth, const int32_t* nug_pidx, float dist_max, float thr_close,
+                                       float thr_avg, float* t, float* dist, float* dist_prev, uint8_t* mask, uint8_t* hit,
+                                       const int32_t* curr_in, int32_t* curr_out, int64_t* curr_pidx, float* x,
+                                       const float* const* planes, const int32_t* sizes, int num_lods, int feature_dim,
+                                       int multiscale, const float* w1, const float* b1, const float* w2, const float* b2,
+                                       int hidden, float scale, int32_t* any_active, wisp_stream_t stream);
+
 /* One optimisation step's forward + loss + backward of the reference's SDFTrainer (wisp/trainers/sdf_trainer.py:65-124 with
- * only_last: loss = sum((pred - gt)^2) / n) for that field (csrc/hash_sdf_train.hip): what autograd runs over
+ * only_last: loss = sum((pred - gt)^2) / n) for the hash field (csrc/hash_sdf_train.hip): what autograd runs over
  * HashGrid.interpolate (wisp/models/grids/hash_grid.py:205-233; backward kernels hashgrid_interpolate_cuda.cu:214-339) and the decoder
  * (wisp/models/nefs/neural_sdf.py:120-155), in two launches.  The hash-grid twin of wisp_sdf_train_step.
  *  coords f32 [n,3], gts f32 [n], n >= 1; the hash field as above with feats_dtype f32 (the only table dtype under training);

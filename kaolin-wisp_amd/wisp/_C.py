@@ -93,6 +93,11 @@ SIGNATURES = {
     "wisp_hash_sdf_trace_step_fused": [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                        c_f32, c_vp, c_vp],
+    "wisp_triplane_sdf_query": [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "wisp_triplane_sdf_fd_gradient": [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp, c_vp],
+    "wisp_triplane_sdf_trace_step_fused": [c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp,
+                                           c_vp],
     "wisp_hash_sdf_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32, c_i32],
     "wisp_hash_sdf_train_step": [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
@@ -1430,39 +1435,72 @@ def _hash_sdf_field_args(fld):
             _p(w1), _p(b1), _p(w2), _p(b2), w1.shape[0]), (bi, rs)
 
 
-def _is_hash_field(fld):
+def _triplane_sdf_field_args(fld):
+    """the field part of the wisp_triplane_sdf_* argument lists from a dict of kind 'triplane' (PackedSDFTracer._fused_field_triplane):
+    planes = [x0, y0, z0, x1, ...], each [1 or -, fdim, R, R] as wisp_triplane_fwd takes them"""
+    planes = fld["planes"]
+    w1, b1, w2, b2 = fld["w1"], fld["b1"], fld["w2"], fld["b2"]
+    L = len(planes) // 3
+    multiscale = {"cat": 0, "sum": 1}[fld["multiscale"]]
+    assert L >= 1 and len(planes) == 3 * L
+    fdim, sizes = int(planes[0].shape[-3]), [int(planes[3 * l].shape[-1]) for l in range(L)]
+    for i, q in enumerate(planes):
+        assert q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.numel() == fdim * sizes[i // 3] ** 2
+        assert q.shape[-3] == fdim and q.shape[-1] == q.shape[-2] == sizes[i // 3]
+    cols = (1 if multiscale else L) * 3 * fdim
+    for a in (w1, b1, w2, b2):
+        assert a.is_cuda and a.dtype == torch.float32 and a.is_contiguous()
+    assert w1.shape[1] == 3 + cols and b1.numel() == w1.shape[0] and w2.numel() == w1.shape[0] and b2.numel() == 1
+    parr, pptr = _ptr_array(planes)
+    sarr, sptr = _host_i32(sizes)
+    return (pptr, sptr, L, fdim, multiscale, _p(w1), _p(b1), _p(w2), _p(b2), w1.shape[0]), (parr, sarr)
+
+
+def _field_kind(fld):
     kind = fld.get("kind", "octree")
-    if kind not in ("octree", "hash"):
+    if kind not in ("octree", "hash", "triplane"):
         raise ValueError(f"unknown fused SDF field kind {kind!r}")
-    return kind == "hash"
+    return kind
+
+
+def _is_hash_field(fld):
+    return _field_kind(fld) == "hash"
+
+
+# per kind of field dict: its argument list, and the query / gradient / marching entry points over it
+_SDF_FIELD_ARGS = {"octree": _sdf_field_args, "hash": _hash_sdf_field_args, "triplane": _triplane_sdf_field_args}
+_SDF_QUERY_FN = {"octree": lib.wisp_sdf_query, "hash": lib.wisp_hash_sdf_query, "triplane": lib.wisp_triplane_sdf_query}
+_SDF_GRADIENT_FN = {"octree": lib.wisp_sdf_fd_gradient, "hash": lib.wisp_hash_sdf_fd_gradient,
+                    "triplane": lib.wisp_triplane_sdf_fd_gradient}
 
 
 def sdf_query(coords, fld, gts=None, counts=None, with_out=True):
     """Field values at coords [n,3] -> f32 [n, rows] (rows = 1, or 4 for a textured field: the decoder's raw outputs), one launch
-    (csrc/sdf_eval.hip; a field dict of kind 'hash': csrc/hash_sdf_eval.hip).  gts [n] + counts (int64 [2], ADDED to):
-    intersection / union of (pred < 0), (gt < 0) on the distance row; with_out=False returns None and only counts."""
-    hashed = _is_hash_field(fld)
+    (csrc/sdf_eval.hip; a field dict of kind 'hash': csrc/hash_sdf_eval.hip, of kind 'triplane': csrc/triplane_sdf_eval.hip).
+    gts [n] + counts (int64 [2], ADDED to): intersection / union of (pred < 0), (gt < 0) on the distance row; with_out=False
+    returns None and only counts."""
+    kind = _field_kind(fld)
     coords = _need(coords, torch.float32, "coords")
     n = coords.shape[0]
-    args, keep = _hash_sdf_field_args(fld) if hashed else _sdf_field_args(fld)
-    out = torch.empty(n, 1 if hashed else args[-1], dtype=torch.float32, device=coords.device) if with_out else None
+    args, keep = _SDF_FIELD_ARGS[kind](fld)
+    out = torch.empty(n, args[-1] if kind == "octree" else 1, dtype=torch.float32, device=coords.device) if with_out else None
     if counts is not None:
         gts = _need(gts, torch.float32, "gts").reshape(-1)
         assert gts.shape[0] == n and counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
-    fn = lib.wisp_hash_sdf_query if hashed else lib.wisp_sdf_query
+    fn = _SDF_QUERY_FN[kind]
     _check(fn(_p(coords), n, *args, _p(out), _p(gts) if counts is not None else c_vp(0), _p(counts), _stream()), "sdf_query")
     return out
 
 
 def sdf_fd_gradient(coords, fld, eps=0.005):
     """Central-difference gradient [n,3] of the field's distance row at coords [n,3], one launch (csrc/sdf_eval.hip; kind 'hash':
-    csrc/hash_sdf_eval.hip)."""
+    csrc/hash_sdf_eval.hip; kind 'triplane': csrc/triplane_sdf_eval.hip)."""
     coords = _need(coords, torch.float32, "coords")
     n = coords.shape[0]
-    hashed = _is_hash_field(fld)
-    args, keep = _hash_sdf_field_args(fld) if hashed else _sdf_field_args(fld)
+    kind = _field_kind(fld)
+    args, keep = _SDF_FIELD_ARGS[kind](fld)
     grad = torch.empty(n, 3, dtype=torch.float32, device=coords.device)
-    fn = lib.wisp_hash_sdf_fd_gradient if hashed else lib.wisp_sdf_fd_gradient
+    fn = _SDF_GRADIENT_FN[kind]
     _check(fn(_p(coords), n, *args, float(np.float32(eps)), _p(grad), _stream()), "sdf_fd_gradient")
     return grad
 
@@ -1478,10 +1516,21 @@ def hash_sdf_trace_step_fused(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max
            "hash_sdf_trace_step_fused")
 
 
+def triplane_sdf_trace_step_fused(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask,
+                                  hit, curr_in, curr_out, curr_pidx, x, fld, scale, any_active=None):
+    """sphere_trace_step + the NeuralSDF / TriplanarGrid field query at the new positions, one launch (csrc/triplane_sdf_eval.hip)."""
+    args, keep = _triplane_sdf_field_args(fld)
+    _check(lib.wisp_triplane_sdf_trace_step_fused(nug_o.shape[0], int(first), _p(nug_o), _p(nug_d), _p(nug_depth), _p(nug_pidx),
+                                                  float(np.float32(dist_max)), float(np.float32(thr_close)),
+                                                  float(np.float32(thr_avg)), _p(t), _p(dist), _p(dist_prev), _p(mask), _p(hit),
+                                                  _p(curr_in), _p(curr_out), _p(curr_pidx), _p(x), *args, float(np.float32(scale)),
+                                                  _p(any_active), _stream()), "triplane_sdf_trace_step_fused")
+
+
 def sdf_trace_step_field(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit,
                          curr_in, curr_out, curr_pidx, x, fld, scale, any_active=None):
     """One fused marching iteration on a field dict of PackedSDFTracer._fused_field: the entry point goes by its `kind`."""
-    step = hash_sdf_trace_step_fused if _is_hash_field(fld) else sdf_trace_step_fused
+    step = {"octree": sdf_trace_step_fused, "hash": hash_sdf_trace_step_fused, "triplane": triplane_sdf_trace_step_fused}[_field_kind(fld)]
     return step(first, nug_o, nug_d, nug_depth, nug_pidx, dist_max, thr_close, thr_avg, t, dist, dist_prev, mask, hit, curr_in,
                 curr_out, curr_pidx, x, fld, scale, any_active)
 

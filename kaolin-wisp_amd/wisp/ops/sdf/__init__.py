@@ -1,6 +1,6 @@
 """Evaluation of signed-distance fields: the IoU metric of the reference (wisp/ops/sdf/metrics.py) and one-launch queries of an
-nglod-shaped field (csrc/sdf_eval.hip over an OctreeGrid, csrc/hash_sdf_eval.hip over a HashGrid) with the modular path as the
-fallback for every other shape."""
+nglod-shaped field (csrc/sdf_eval.hip over an OctreeGrid, csrc/hash_sdf_eval.hip over a HashGrid, csrc/triplane_sdf_eval.hip over a
+TriplanarGrid) with the modular path as the fallback for every other shape."""
 import torch
 
 from wisp.ops.differential import finitediff_gradient
@@ -22,7 +22,10 @@ def fused_sdf_field(nef, lod_idx=None):
     WISP_SDF_FUSED=0 switches the kernels off.  A textured field keeps all four output rows in module order (rgb logits, then
     the distance).  A plain NeuralSDF over a 3-D HashGrid (nglod_hash.yaml) yields a dict of kind 'hash' for
     wisp_hash_sdf_query / wisp_hash_sdf_fd_gradient (PackedSDFTracer._fused_field_hash: feature_dim 2 / 4 / 8, at most 32
-    feature columns, the same decoder shape); there every lod_idx of the grid is served, 0 included."""
+    feature columns, the same decoder shape); there every lod_idx of the grid is served, 0 included.  A plain NeuralSDF over a
+    TriplanarGrid (nglod_triplanar.yaml) yields a dict of kind 'triplane' for wisp_triplane_sdf_query /
+    wisp_triplane_sdf_fd_gradient (PackedSDFTracer._fused_field_triplane: f32 planes, at most 48 feature columns, the same decoder
+    shape; 'sum' at every lod_idx, 'cat' at the last one)."""
     from wisp.tracers.packed_sdf_tracer import PackedSDFTracer
     grid = getattr(nef, "grid", None)
     if grid is None or not hasattr(grid, "num_lods"):

@@ -90,9 +90,10 @@ class PackedSDFTracer(BaseTracer):
         input without embedding, one hidden relu layer with bias.  A NeuralSDFTex of the same shape (four outputs; features
         alone, or the raw position in front of them) marches on its fourth output row.  Anything else marches through
         `nef(...)` per iteration.  A plain NeuralSDF over a HashGrid (nglod_hash.yaml) has a branch of its own:
-        _fused_field_hash."""
+        _fused_field_hash; so has one over a TriplanarGrid (nglod_triplanar.yaml): _fused_field_triplane."""
         from wisp.models.grids.hash_grid import HashGrid
         from wisp.models.grids.octree_grid import OctreeGrid
+        from wisp.models.grids.triplanar_grid import TriplanarGrid
         from wisp.models.nefs.neural_sdf import NeuralSDF
         from wisp.models.nefs.neural_sdf_tex import NeuralSDFTex
         import os
@@ -100,6 +101,8 @@ class PackedSDFTracer(BaseTracer):
             return None
         if type(nef.grid) is HashGrid:
             return PackedSDFTracer._fused_field_hash(nef, lod_idx) if type(nef) is NeuralSDF else None
+        if type(nef.grid) is TriplanarGrid:
+            return PackedSDFTracer._fused_field_triplane(nef, lod_idx) if type(nef) is NeuralSDF else None
         if type(nef.grid) is not OctreeGrid:
             return None
         if type(nef) is NeuralSDFTex:
@@ -169,6 +172,29 @@ class PackedSDFTracer(BaseTracer):
                     resolutions=[int(r) for r in g.resolutions], feature_dim=int(g.feature_dim),
                     codebook_bitwidth=int(g.codebook_bitwidth), multiscale=g.multiscale_type,
                     zero_from_col=(lod_idx if cat else g.num_lods) * g.feature_dim,
+                    w1=dec.layers[0].weight.detach().float().contiguous(), b1=dec.layers[0].bias.detach().float().contiguous(),
+                    w2=dec.lout.weight.detach().float().reshape(-1).contiguous(), b2=dec.lout.bias.detach().float().contiguous())
+
+    @staticmethod
+    def _fused_field_triplane(nef, lod_idx):
+        """_fused_field for a plain NeuralSDF over a TriplanarGrid (csrc/triplane_sdf_eval.hip): linear interpolation, f32 planes
+        on the GPU, at most 48 feature columns ('cat': (lod_idx + 1) * 3 * features per plane, 'sum': 3 * features per plane), raw
+        position input without embedding, one hidden relu layer of at most 256 units with biases, one output.  0 <= lod_idx <
+        num_lods; 'cat' only at the last level - below it TriplanarGrid.interpolate returns fewer columns than the decoder has.
+        The dict carries kind='triplane' and the planes of the levels 0..lod_idx; wisp._C dispatches on the kind."""
+        g, dec = nef.grid, nef.decoder
+        if (g.multiscale_type not in ('cat', 'sum') or g.interpolation_type != 'linear'
+                or not 1 <= g.num_lods <= 16 or not 0 <= lod_idx < g.num_lods
+                or (g.multiscale_type == 'cat' and lod_idx != g.num_lods - 1)
+                or not nef.position_input or not isinstance(nef.pos_embedder, torch.nn.Identity)
+                or not PackedSDFTracer._fused_decoder(nef, 1)):
+            return None
+        planes = [p for i in range(lod_idx + 1) for p in (g.features[i].fmx, g.features[i].fmy, g.features[i].fmz)]
+        cols = (lod_idx + 1 if g.multiscale_type == 'cat' else 1) * g.feature_dim          # (the grid's feature_dim is 3 x per plane)
+        if (cols > 48 or dec.layers[0].in_features != 3 + cols
+                or any(not p.is_cuda or p.dtype != torch.float32 for p in planes)):
+            return None
+        return dict(kind='triplane', planes=[p.detach().contiguous() for p in planes], multiscale=g.multiscale_type,
                     w1=dec.layers[0].weight.detach().float().contiguous(), b1=dec.layers[0].bias.detach().float().contiguous(),
                     w2=dec.lout.weight.detach().float().reshape(-1).contiguous(), b2=dec.lout.bias.detach().float().contiguous())
 

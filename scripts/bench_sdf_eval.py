@@ -11,6 +11,9 @@ synchronisation (the host work between launches is part of what is compared):
 
 --grid hash measures the same three on the field of nglod_hash.yaml (HashGrid.from_geometric, 'cat', 4 levels x 8 features, 16 ..
 2048, tables of 2^--codebook-bitwidth rows; csrc/hash_sdf_eval.hip) and writes profiles/bench_hash_sdf_eval.json.
+--grid triplanar measures them on the field of nglod_triplanar.yaml (TriplanarGrid, 'sum', one level of three 4 x 33 x 33 planes over
+an AxisAlignedBBoxAS, MeshSampledSDFDataset; csrc/triplane_sdf_eval.hip), fitted with SDFTrainer (the field has no fused training
+step), and writes profiles/bench_triplanar_sdf_eval.json; every timing also carries the maximum of its repetitions.
 """
 import argparse
 import json
@@ -47,6 +50,7 @@ def compare(fn, reps):
     os.environ["WISP_SDF_FUSED"] = "1"
     out = {f"{m}_ms_median": round(statistics.median(v), 4) for m, v in times.items()}
     out.update({f"{m}_ms_min": round(min(v), 4) for m, v in times.items()})
+    out.update({f"{m}_ms_max": round(max(v), 4) for m, v in times.items()})
     out["speedup_median"] = round(out["modular_ms_median"] / out["fused_ms_median"], 3)
     return out
 
@@ -58,12 +62,14 @@ def main(argv=None):
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--epochs", type=int, default=2, help="epochs of fitting before measuring (the render needs a surface)")
-    ap.add_argument("--grid", choices=("octree", "hash"), default="octree")
+    ap.add_argument("--grid", choices=("octree", "hash", "triplanar"), default="octree")
     ap.add_argument("--codebook-bitwidth", type=int, default=19, help="--grid hash: the hashed levels have 2^N rows")
-    ap.add_argument("--out", default=None, help="default: profiles/bench_sdf_eval.json, bench_hash_sdf_eval.json with --grid hash")
+    ap.add_argument("--out", default=None, help="default: profiles/bench_sdf_eval.json, bench_hash_sdf_eval.json with --grid hash, "
+                                               "bench_triplanar_sdf_eval.json with --grid triplanar")
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "bench_hash_sdf_eval.json" if args.grid == "hash" else "bench_sdf_eval.json")
+        args.out = os.path.join(ROOT, "profiles", {"hash": "bench_hash_sdf_eval.json", "triplanar": "bench_triplanar_sdf_eval.json"}
+                                .get(args.grid, "bench_sdf_eval.json"))
     logging.basicConfig(level=logging.WARNING)
     import train_nglod
     from train_sdf_tex import write_test_mesh
@@ -80,10 +86,14 @@ def main(argv=None):
     cfg = ConfigSDFTrainer(optimizer=ConfigAdam(lr=1e-3, eps=1e-15), dataloader=ConfigDataloader(batch_size=512),
                            max_epochs=args.epochs, resample=False, only_last=True, profile_nvtx=False)
     trainer = SDFTrainer(cfg, pipeline, ds, device=dev)
-    train_nglod.fit_fused(trainer, ds, cfg, dev)
+    if args.grid == "triplanar":
+        trainer.train()
+        pipeline.eval()
+    else:
+        train_nglod.fit_fused(trainer, ds, cfg, dev)
     nef = pipeline.nef
     assert fused_sdf_field(nef, None) is not None
-    rec = dict(bench="hash_sdf_eval" if args.grid == "hash" else "sdf_eval", device=torch.cuda.get_device_name(0), level=args.level,
+    rec = dict(bench={"hash": "hash_sdf_eval", "triplanar": "triplanar_sdf_eval"}.get(args.grid, "sdf_eval"), device=torch.cuda.get_device_name(0), level=args.level,
                lods=nef.grid.num_lods, hidden=128, **(dict(codebook_bitwidth=args.codebook_bitwidth) if args.grid == "hash" else {}),
                dataset_points=len(ds), batches=len(trainer.train_data_loader), reps=args.reps)
     iou = {}

@@ -2,7 +2,7 @@
 OctreeAS.from_mesh, OctreeGrid, NeuralSDF, a mesh SDF dataset, SDFTrainer with its IoU validation - then an OfflineRenderer
 snapshot (render.png) and the three axis-aligned distance cross-sections (slice_x.png, slice_y.png, slice_z.png).
 
-    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--grid octree|hash] [--fused-step] [--out-dir DIR]
+    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--grid octree|hash|triplanar] [--fused-step] [--out-dir DIR]
     python scripts/train_nglod.py --write-test-mesh DIR ...
 
 --write-test-mesh DIR first writes the procedural torus of scripts/train_sdf_tex.py into DIR and fits that.
@@ -13,6 +13,10 @@ as a HIP graph for whole batches) instead of SDFTrainer's torch.optim loop; vali
 the kernels of csrc/hash_sdf_eval.hip, and --fused-step trains through wisp_hash_sdf_train_step (csrc/hash_sdf_train.hip:
 SDFTrainStep(..., fused_hash=True)), replayed as a HIP graph like the octree step; the JSON record's fused_hash_step says whether
 the field took that branch.
+--grid triplanar fits the field of nglod_triplanar.yaml: AxisAlignedBBoxAS, TriplanarGrid of one level of three 4 x 33 x 33
+planes, 'sum', and the configuration's MeshSampledSDFDataset (--dataset mesh is implied).  Validation, the snapshot and the slices
+run through the kernels of csrc/triplane_sdf_eval.hip; the JSON record's fused_triplane_eval says whether the field took them.
+There is no fused training step for this field: --grid triplanar --fused-step is refused.
 The last line printed is one JSON record with the IoU before and after training."""
 import argparse
 import json
@@ -30,13 +34,20 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "kaolin-wisp_amd"), os.path.join(ROOT, 
 
 def build(obj, device, level=6, dataset="octree", num_samples=100000, samples_per_voxel=16, num_lods=4, hidden_dim=128,
           num_samples_on_mesh=2_000_000, grid_type="octree", codebook_bitwidth=19):
-    """(dataset, pipeline) as main_nglod.py builds them from nglod_octree.yaml (grid_type 'octree') or nglod_hash.yaml ('hash')."""
-    from wisp.accelstructs import OctreeAS
+    """(dataset, pipeline) as main_nglod.py builds them from nglod_octree.yaml (grid_type 'octree'), nglod_hash.yaml ('hash') or
+    nglod_triplanar.yaml ('triplanar')."""
+    from wisp.accelstructs import AxisAlignedBBoxAS, OctreeAS
     from wisp.datasets import MeshSampledSDFDataset, OctreeSampledSDFDataset
     from wisp.models import Pipeline
-    from wisp.models.grids import HashGrid, OctreeGrid
+    from wisp.models.grids import HashGrid, OctreeGrid, TriplanarGrid
     from wisp.models.nefs import NeuralSDF
     from wisp.tracers import PackedSDFTracer
+    if grid_type == "triplanar":
+        ds = MeshSampledSDFDataset(obj, split='train', num_samples=max(num_samples // 5, 1))
+        grid = TriplanarGrid(AxisAlignedBBoxAS(), feature_dim=4, log_base_resolution=5, num_lods=1, multiscale_type='sum',
+                             feature_std=0.01)
+        nef = NeuralSDF(grid, pos_embedder='none', position_input=True, hidden_dim=hidden_dim, num_layers=1).to(device)
+        return ds, Pipeline(nef, PackedSDFTracer(num_steps=128, step_size=0.8, min_dis=0.0003))
     blas = OctreeAS.from_mesh(obj, level=level, num_samples_on_mesh=num_samples_on_mesh)
     if dataset == "octree":
         ds = OctreeSampledSDFDataset(blas, split='train', num_samples=num_samples, samples_per_voxel=samples_per_voxel)
@@ -80,12 +91,15 @@ def fit_fused(trainer, ds, cfg, device):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter,
+                                 epilog="--grid {octree,hash} take either --dataset and --fused-step;\n"
+                                        "--grid triplanar implies --dataset mesh and has no fused training step.")
     ap.add_argument("obj", nargs="?")
     ap.add_argument("--write-test-mesh", metavar="DIR")
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--dataset", choices=("octree", "mesh"), default="octree")
-    ap.add_argument("--grid", choices=("octree", "hash"), default="octree", help="feature grid: nglod_octree.yaml or nglod_hash.yaml")
+    ap.add_argument("--grid", choices=("octree", "hash", "triplanar"), default="octree",
+                    help="feature grid: nglod_octree.yaml, nglod_hash.yaml or nglod_triplanar.yaml")
     ap.add_argument("--codebook-bitwidth", type=int, default=19, help="--grid hash: the hashed levels have 2^N rows")
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--num-lods", type=int, default=4)
@@ -100,6 +114,10 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.grid == "triplanar":
+        if args.fused_step:
+            ap.error("--grid triplanar has no fused training step: drop --fused-step")
+        args.dataset = "mesh"
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     from wisp.ops.image import save_u8
     from wisp.trainers import ConfigAdam, ConfigDataloader, ConfigSDFTrainer, SDFTrainer
@@ -119,6 +137,9 @@ def main(argv=None):
                            max_epochs=args.epochs, resample=True, only_last=True, exp_name='nglod', profile_nvtx=False,
                            valid_every=-1)
     trainer = SDFTrainer(cfg, pipeline, ds, device=args.device)
+    from wisp.ops.sdf import fused_sdf_field
+    fld = fused_sdf_field(pipeline.nef) if torch.device(args.device).type == 'cuda' else None
+    fused_triplane_eval = bool(args.grid == "triplanar" and fld is not None and fld.get("kind") == "triplane")
     before = trainer.validate()
     metric = next(iter(before))
     t0 = time.time()
@@ -145,7 +166,7 @@ def main(argv=None):
         vis = renderer.sdf_slice(pipeline.nef, dim=axis)
         save_u8(files[f"slice_{name}"], (np.clip(vis, 0, 1) * 255).round().astype(np.uint8).transpose(1, 0, 2))
     rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, grid=args.grid, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
-               fused_hash_step=fused_hash_step,
+               fused_hash_step=fused_hash_step, fused_triplane_eval=fused_triplane_eval,
                metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
                seconds=round(seconds, 3), **{k: os.path.abspath(v) for k, v in files.items()})
     print(json.dumps(rec))
