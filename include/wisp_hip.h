@@ -44,7 +44,7 @@ const char* wisp_last_error(void);
  * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_nerf_query, wisp_composite_loss_partials, wisp_loss_sum,
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
  * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim, wisp_triplane_sdf_query,
- * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused, wisp_triplane_sdf_train_step - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -671,6 +671,30 @@ int wisp_hash_sdf_train_step(const float* coords, const float* gts, int64_t n, c
                              const float* w2, const float* b2, int hidden, float* grad_codebook, float* grad_w1, float* grad_b1,
                              float* grad_w2, float* grad_b2, float* loss, void* scratch, int64_t scratch_bytes,
                              wisp_stream_t stream);
+
+/* The same step for the triplanar field of wisp_triplane_sdf_query (csrc/triplane_sdf_train.hip; wisp/trainers/sdf_trainer.py:65-124
+ * with only_last): what autograd runs over TriplanarGrid.interpolate (wisp/models/grids/triplanar_grid.py:97-146, :205-233) and the
+ * decoder, in one memset and two launches.  The triplanar twin of wisp_hash_sdf_train_step.
+ *  coords f32 [n,3], gts f32 [n], n >= 1; planes / sizes / num_lods / feature_dim / multiscale / w1 .. hidden as for
+ *  wisp_triplane_sdf_query (f32 planes, up to 16 levels, 48 feature columns, hidden 256);
+ *  grad_planes: HOST array of 3 * num_lods DEVICE pointers in the order of `planes`, each of its plane's shape; grad_w1 / grad_b1 /
+ *  grad_w2 / grad_b2 of their parameters' shapes: all are ADDED to; loss f32 [1] is written.  The predicted distance is bit for bit
+ *  wisp_triplane_sdf_query's.  A corner that the forward leaves out (x0 + 1 or y0 + 1 outside the plane) receives nothing; under
+ *  'sum' every level receives the gradient of the summed column.
+ *  scratch: wisp_triplane_sdf_train_scratch_bytes(...) bytes, contents irrelevant - the partial rows and the fp64 accumulators of the
+ *  planes of at most 2^16 entries (feature_dim * size^2), which is why it takes `sizes`; that function returns -1 for a shape the
+ *  step does not serve, and the step then returns WISP_ERR_INVALID before any launch, as for every other failed check (the limits
+ *  above, a null pointer, n < 1, a scratch that is too small).
+ * The loss and the decoder's four gradients have a fixed summation order: bitwise repeatable.  A plane of at most 2^16 entries is
+ * summed with fp64 atomic adds of exact products into scratch and rounded once, a larger one with f32 atomic adds: repeatable only
+ * where the sums are exact. */
+int64_t wisp_triplane_sdf_train_scratch_bytes(int64_t n, const int32_t* sizes, int num_lods, int feature_dim, int multiscale,
+                                              int hidden);
+int wisp_triplane_sdf_train_step(const float* coords, const float* gts, int64_t n, const float* const* planes,
+                                 const int32_t* sizes, int num_lods, int feature_dim, int multiscale, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, int hidden, float* const* grad_planes,
+                                 float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, float* loss, void* scratch,
+                                 int64_t scratch_bytes, wisp_stream_t stream);
 
 /* Compositing + photometric loss + compositing backward of a TRAINING step in one launch (what
  * wisp/tracers/packed_rf_tracer.py:143-165, wisp/trainers/multiview_trainer.py:140-154 and their autograd backward do in

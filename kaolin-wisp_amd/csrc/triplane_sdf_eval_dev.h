@@ -3,8 +3,9 @@
 // F.grid_sample lookups with align_corners=True and reflection padding - plane x with (y, z), plane y with (x, z), plane z with
 // (x, y) - stacked as [x | y | z], the levels 'cat'-ed behind one another or 'sum'-med -> [position, features] -> Linear -> relu
 // -> Linear).  The triplanar twin of hash_sdf_eval_point (hash_sdf_eval_dev.h); shared by the three kernels of
-// triplane_sdf_eval.hip, so that a value the gradient kernel differences and a distance the marching kernel steps by are bit for
-// bit what the query kernel returns for the same position.
+// triplane_sdf_eval.hip and the training step of triplane_sdf_train.hip, so that a value the gradient kernel differences, a
+// distance the marching kernel steps by and a prediction the training step takes its loss from are bit for bit what the query
+// kernel returns for the same position.
 //
 // 16 lanes own one point.  Lane c blends the feature columns c, c + 16, ... (at most three: K <= 48).  A column is one (plane,
 // channel) of one level ('cat') or of every level ('sum': the lane adds its column's levels itself in level order in fp32, so
@@ -18,8 +19,8 @@
 // sdf_eval_coeffs (sdf_eval_dev.h).  triplane_kernel (spc_interp.hip) leaves its contraction to the compiler, so the two agree
 // to rounding, not bit for bit.
 //
-// The end of the file is HOST code: tri_sdf_fill, the shape and pointer checks that fill a TriSdfField, shared by the three entry
-// points.
+// The end of the file is HOST code: tri_sdf_fill, the shape and pointer checks that fill a TriSdfField, shared by the entry points
+// of both files.
 #pragma once
 #include "wisp_common.h"
 #include "grid_sample_dev.h"
@@ -82,6 +83,23 @@ static __device__ __forceinline__ float tri_sdf_blend(const float* __restrict__ 
     return v;
 }
 
+// The integer corner and the four weights of that lookup, for the training step's scatter (triplane_sdf_train.hip): the statements
+// of tri_sdf_blend, so the same bits.  off: the offset of texel (y0, x0) of channel ch inside the plane.
+struct TriSdfCorner { int64_t off; float w00, w01, w10, w11; bool vx1, vy1; };
+static __device__ __forceinline__ TriSdfCorner tri_sdf_corner(int R, int ch, float gx, float gy) {
+#pragma clang fp contract(off)
+    const float ix = wisp_reflect_source_index(gx, R), iy = wisp_reflect_source_index(gy, R);
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy;                      // in [0, R - 1] for every input (grid_sample_dev.h)
+    const float tx = ix - fx, ty = iy - fy;
+    const float ux = 1.0f - tx, uy = 1.0f - ty;
+    TriSdfCorner k;
+    k.w00 = ux * uy; k.w01 = tx * uy; k.w10 = ux * ty; k.w11 = tx * ty;
+    k.vx1 = x0 + 1 < R; k.vy1 = y0 + 1 < R;
+    k.off = (int64_t)ch * R * R + (int64_t)y0 * R + x0;
+    return k;
+}
+
 // tri_sdf_point_inputs: the decoder inputs [position, features] of one position into gin[0 .. 3 + cols).  All 16 lanes of a group
 // call it together, with the same position; c = lane within the group.  Ends with the wave barrier that makes them visible to the
 // group.
@@ -104,8 +122,11 @@ static __device__ __forceinline__ void tri_sdf_point_inputs(const TriSdfField& f
 }
 
 // tri_sdf_decode: the decoder over gin, in = [position, features]; returns the raw output with the bias added (hash_sdf_decode's
-// statements).
-static __device__ __forceinline__ float tri_sdf_decode(const TriSdfField& fld, const TriSdfLds& s, const float* gin, int c) {
+// statements).  KEEP (the training step): lane c also leaves, for its hidden units hh = c, c + 16, ..., w2[hh] where the unit is
+// active (0 elsewhere) in ga[hh] and the unit's relu output in gr[hh] - stores only, the arithmetic is the same statements.
+template <bool KEEP = false>
+static __device__ __forceinline__ float tri_sdf_decode(const TriSdfField& fld, const TriSdfLds& s, const float* gin, int c,
+                                                       float* ga = nullptr, float* gr = nullptr) {
 #pragma clang fp contract(off)
     const int in_dim = 3 + fld.cols;
     float o = 0.0f;
@@ -114,6 +135,10 @@ static __device__ __forceinline__ float tri_sdf_decode(const TriSdfField& fld, c
         float a = s.b1[hh];
         for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
         o = __builtin_fmaf(s.w2[hh], fmaxf(a, 0.0f), o);
+        if (KEEP) {
+            ga[hh] = a > 0.0f ? s.w2[hh] : 0.0f;
+            gr[hh] = fmaxf(a, 0.0f);
+        }
     }
 #pragma unroll
     for (int d = TSDF_GROUP / 2; d >= 1; d >>= 1) o += __shfl_xor(o, d, TSDF_GROUP);

@@ -101,6 +101,9 @@ SIGNATURES = {
     "wisp_hash_sdf_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32, c_i32],
     "wisp_hash_sdf_train_step": [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "wisp_triplane_sdf_train_scratch_bytes": [c_i64, c_vp, c_i32, c_i32, c_i32, c_i32],
+    "wisp_triplane_sdf_train_step": [c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "wisp_sdf_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32],
     "wisp_sdf_train_step": [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
@@ -180,7 +183,7 @@ SIGNATURES = {
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
-_RESTYPES = {"wisp_ssim_scratch_bytes": c_i64, "wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
+_RESTYPES = {"wisp_ssim_scratch_bytes": c_i64, "wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_triplane_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
              "wisp_last_error": ctypes.c_char_p, "wisp_host_reader_create": c_vp, "wisp_host_reader_destroy": None,
              "wisp_nerf_step_config_bytes": c_i64, "wisp_nerf_step_workspace_bytes": c_i64, "wisp_nerf_step_create": c_vp,
              "wisp_nerf_step_destroy": None}
@@ -1625,6 +1628,33 @@ def hash_sdf_train_step(coords, gts, fld, grad_codebook, grad_w1, grad_b1, grad_
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     _check(lib.wisp_hash_sdf_train_step(_p(coords), _p(gts), n, *args, _p(grad_codebook), _p(grad_w1), _p(grad_b1), _p(grad_w2),
                                         _p(grad_b2), _p(loss), _p(scratch), scratch.numel(), _stream()), "hash_sdf_train_step")
+    return loss
+
+
+def triplane_sdf_train_step(coords, gts, fld, grad_planes, grad_w1, grad_b1, grad_w2, grad_b2):
+    """Forward + loss + backward of one SDF regression step over a triplanar field (wisp_triplane_sdf_train_step; fld: a dict of
+    kind 'triplane', PackedSDFTracer._fused_field_triplane): coords [n,3], gts [n,1] -> loss f32 [1] (= sum((pred - gt)^2) / n); the
+    gradients are ADDED to grad_planes (list, one per plane in the order of fld['planes']) and grad_w1 / b1 / w2 / b2."""
+    if _field_kind(fld) != "triplane":
+        raise ValueError("triplane_sdf_train_step: the field dict is not of kind 'triplane'")
+    coords = _need(coords, torch.float32, "coords")
+    gts = _need(gts, torch.float32, "gts").reshape(-1)
+    n, dev = coords.shape[0], coords.device
+    args, keep = _triplane_sdf_field_args(fld)
+    planes, w1 = fld["planes"], fld["w1"]
+    sptr, L, F, multiscale, H = args[1], args[2], args[3], args[4], w1.shape[0]
+    assert gts.shape[0] == n and tuple(coords.shape) == (n, 3) and len(grad_planes) == len(planes)
+    for g, q in list(zip(grad_planes, planes)) + [(grad_w1, w1), (grad_b1, fld["b1"]), (grad_w2, fld["w2"]), (grad_b2, fld["b2"])]:
+        assert g.device == dev and q.device == dev and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == q.numel()
+    assert tuple(grad_w1.shape) == tuple(w1.shape)
+    need = int(lib.wisp_triplane_sdf_train_scratch_bytes(n, sptr, L, F, multiscale, H))
+    if need < 0:
+        raise RuntimeError(f"triplane_sdf_train_step: unsupported shape (n {n}, lods {L}, feature_dim {F}, hidden {H})")
+    scratch = _sdf_scratch.get(dev, need)
+    garr, gptr = _ptr_array(grad_planes)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    _check(lib.wisp_triplane_sdf_train_step(_p(coords), _p(gts), n, *args, gptr, _p(grad_w1), _p(grad_b1), _p(grad_w2), _p(grad_b2),
+                                            _p(loss), _p(scratch), scratch.numel(), _stream()), "triplane_sdf_train_step")
     return loss
 
 

@@ -25,11 +25,13 @@ def _hip():
 
 class SDFTrainStep:
     def __init__(self, nef, lr=1e-3, eps=1e-15, weight_decay=0.0, grid_lr_weight=1.0, betas=(0.9, 0.999), optimizer='adam',
-                 only_last=True, alpha=0.99, momentum=0.0, fused_hash=False):
+                 only_last=True, alpha=0.99, momentum=0.0, fused_hash=False, fused_triplane=False):
         self.nef = nef
         # opt-in: a NeuralSDF over a HashGrid trains through wisp_hash_sdf_train_step (see _fused_field); a trainer built without
         # it keeps the modular launches over a hash grid, with the results it always had
         self.fused_hash = bool(fused_hash)
+        # opt-in, likewise: a NeuralSDF over a TriplanarGrid trains through wisp_triplane_sdf_train_step
+        self.fused_triplane = bool(fused_triplane)
         self.flat = FlatParams(nef)
         self.lr, self.eps, self.weight_decay, self.grid_lr_weight, self.betas = lr, eps, weight_decay, grid_lr_weight, betas
         self.optimizer = str(optimizer).lower()
@@ -67,7 +69,8 @@ class SDFTrainStep:
         biases, one output) over [position, 'sum' OctreeGrid features of 16 channels], fp32 parameters living in the flat
         buffers, loss on the finest LOD only.  A NeuralSDFTex (four outputs; features alone, or the identity position in front
         of them) gets what wisp_sdf_tex_train_step needs under the same gates.  A plain NeuralSDF over a HashGrid gets what
-        wisp_hash_sdf_train_step needs (_fused_field_hash) - only in a trainer built with fused_hash=True.
+        wisp_hash_sdf_train_step needs (_fused_field_hash) - only in a trainer built with fused_hash=True; one over a TriplanarGrid
+        what wisp_triplane_sdf_train_step needs (_fused_field_triplane) - only in a trainer built with fused_triplane=True.
         WISP_SDF_TRAIN_FUSED=0 keeps the modular launches."""
         import os
         if getattr(self, "_fused_seen_only_last", None) != self.only_last:        # toggled since the decision was taken
@@ -84,12 +87,14 @@ class SDFTrainStep:
         if os.environ.get("WISP_SDF_TRAIN_FUSED", "1") == "0" or not self.only_last:
             return None
         from wisp.accelstructs import OctreeAS
-        from wisp.models.grids import HashGrid, OctreeGrid
+        from wisp.models.grids import HashGrid, OctreeGrid, TriplanarGrid
         from wisp.models.nefs._grid_mlp import _fusable_small_decoder
         nef = self.nef
         grid, dec = getattr(nef, "grid", None), getattr(nef, "decoder", None)
         if type(grid) is HashGrid:
             return self._fused_field_hash(grid, dec) if self.fused_hash and dec is not None else None
+        if type(grid) is TriplanarGrid:
+            return self._fused_field_triplane(grid, dec) if self.fused_triplane and dec is not None else None
         if type(grid) is not OctreeGrid or type(getattr(grid, "blas", None)) is not OctreeAS or dec is None:
             return None
         if self.textured:
@@ -162,13 +167,41 @@ class SDFTrainStep:
         self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm, hash=True, host=host)
         return self._fused_cache
 
+    def _fused_field_triplane(self, grid, dec):
+        """The triplanar branch of _fused_field (the caller has checked the grid's type and the opt-in): a plain NeuralSDF, the shape
+        rules of PackedSDFTracer._fused_field_triplane at the last level, and f32 contiguous planes and decoder whose contiguous f32
+        gradients live in the flat buffers."""
+        from wisp.models.nefs.neural_sdf import NeuralSDF
+        from wisp.tracers import PackedSDFTracer
+        nef = self.nef
+        if type(nef) is not NeuralSDF or self.textured:
+            return None
+        if PackedSDFTracer._fused_field_triplane(nef, grid.num_lods - 1) is None:
+            return None
+        prm = self._triplane_planes(grid) + [dec.layers[0].weight, dec.layers[0].bias, dec.lout.weight, dec.lout.bias]
+        if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.grad is not None and q.grad.is_contiguous()
+                   and q.grad.dtype == torch.float32 for q in prm):
+            return None
+        self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm, triplane=True, multiscale=grid.multiscale_type)
+        return self._fused_cache
+
+    @staticmethod
+    def _triplane_planes(grid):
+        """x, y, z of level 0, then level 1, ...: the plane order of the kernels"""
+        return [p for i in range(grid.num_lods) for p in (grid.features[i].fmx, grid.features[i].fmy, grid.features[i].fmz)]
+
     def _fused_still_valid(self, c):
         nef = self.nef
         grid, dec = c["grid"], c["dec"]
         if not self.only_last or getattr(nef, "grid", None) is not grid or getattr(nef, "decoder", None) is not dec \
                 or grid.num_lods != c["lods"]:
             return False
-        tables = [grid.codebook.feats] if c.get("hash") else list(grid.features[:grid.num_lods])
+        if c.get("triplane"):
+            if grid.multiscale_type != c["multiscale"]:
+                return False
+            tables = self._triplane_planes(grid)
+        else:
+            tables = [grid.codebook.feats] if c.get("hash") else list(grid.features[:grid.num_lods])
         now = tables + [dec.layers[0].weight, dec.layers[0].bias, dec.lout.weight, dec.lout.bias]
         if len(now) != len(c["prm"]):
             return False
@@ -189,6 +222,13 @@ class SDFTrainStep:
                 fld = dict(fused["host"], codebook=table.detach(), w1=w1.detach(), b1=b1.detach(), w2=w2.detach().reshape(-1),
                            b2=b2.detach())
                 return C.hash_sdf_train_step(coords, gts, fld, table.grad, w1.grad, b1.grad, w2.grad.reshape(-1), b2.grad)[0]
+            if fused.get("triplane"):
+                planes = self._triplane_planes(grid)
+                w1, b1, w2, b2 = dec.layers[0].weight, dec.layers[0].bias, dec.lout.weight, dec.lout.bias
+                fld = dict(kind='triplane', planes=[p.detach() for p in planes], multiscale=fused["multiscale"], w1=w1.detach(),
+                           b1=b1.detach(), w2=w2.detach().reshape(-1), b2=b2.detach())
+                return C.triplane_sdf_train_step(coords, gts, fld, [p.grad for p in planes], w1.grad, b1.grad, w2.grad.reshape(-1),
+                                                 b2.grad)[0]
             L = grid.num_lods
             blas = grid.blas
             grid._sync_device(coords.device)

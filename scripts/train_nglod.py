@@ -2,7 +2,8 @@
 OctreeAS.from_mesh, OctreeGrid, NeuralSDF, a mesh SDF dataset, SDFTrainer with its IoU validation - then an OfflineRenderer
 snapshot (render.png) and the three axis-aligned distance cross-sections (slice_x.png, slice_y.png, slice_z.png).
 
-    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--grid octree|hash|triplanar] [--fused-step] [--out-dir DIR]
+    python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--grid octree|hash|triplanar] [--fused-step]
+                                  [--fused-kernel] [--out-dir DIR]
     python scripts/train_nglod.py --write-test-mesh DIR ...
 
 --write-test-mesh DIR first writes the procedural torus of scripts/train_sdf_tex.py into DIR and fits that.
@@ -16,7 +17,9 @@ the field took that branch.
 --grid triplanar fits the field of nglod_triplanar.yaml: AxisAlignedBBoxAS, TriplanarGrid of one level of three 4 x 33 x 33
 planes, 'sum', and the configuration's MeshSampledSDFDataset (--dataset mesh is implied).  Validation, the snapshot and the slices
 run through the kernels of csrc/triplane_sdf_eval.hip; the JSON record's fused_triplane_eval says whether the field took them.
-There is no fused training step for this field: --grid triplanar --fused-step is refused.
+--fused-kernel (with --grid triplanar only) trains this field through wisp_triplane_sdf_train_step (csrc/triplane_sdf_train.hip:
+SDFTrainStep(..., fused_triplane=True)), replayed as a HIP graph for whole batches; the JSON record's fused_triplane_step says
+whether the field took that branch.  --grid triplanar --fused-step stays refused.
 The last line printed is one JSON record with the IoU before and after training."""
 import argparse
 import json
@@ -62,17 +65,18 @@ def build(obj, device, level=6, dataset="octree", num_samples=100000, samples_pe
     return ds, Pipeline(nef, PackedSDFTracer(num_steps=128, step_size=0.8, min_dis=0.0003))
 
 
-def fit_fused(trainer, ds, cfg, device):
-    """SDFTrainer's epochs with SDFTrainStep: shuffled batches of cfg.dataloader.batch_size, resampling after every epoch."""
+def fit_fused(trainer, ds, cfg, device, fused_triplane=False):
+    """SDFTrainer's epochs with SDFTrainStep: shuffled batches of cfg.dataloader.batch_size, resampling after every epoch.  Returns
+    whether the field took its opt-in fused step (the hash one, or with fused_triplane the triplanar one)."""
     from wisp.trainers import SDFTrainStep
     oc, bs = cfg.optimizer, cfg.dataloader.batch_size
     nef = trainer.pipeline.nef
     from wisp.models.grids import HashGrid, OctreeGrid
     step = SDFTrainStep(nef, lr=oc.lr, eps=oc.eps, grid_lr_weight=cfg.grid_lr_weight, betas=oc.betas, optimizer='adam',
-                        only_last=cfg.only_last, fused_hash=type(nef.grid) is HashGrid)
+                        only_last=cfg.only_last, fused_hash=type(nef.grid) is HashGrid, fused_triplane=bool(fused_triplane))
     on_gpu = torch.device(device).type == 'cuda'
-    fused_hash_step = bool(on_gpu and step.fused_hash and step._fused_field() is not None)
-    if on_gpu and len(ds) >= bs and (type(nef.grid) is OctreeGrid or fused_hash_step):
+    took_opt_in = bool(on_gpu and (step.fused_hash or fused_triplane) and step._fused_field() is not None)
+    if on_gpu and len(ds) >= bs and (type(nef.grid) is OctreeGrid or took_opt_in):
         step.capture(bs)
     nef.train()
     for epoch in range(cfg.max_epochs):
@@ -87,13 +91,13 @@ def fit_fused(trainer, ds, cfg, device):
             ds.resample()
             trainer.init_dataloader()
     nef.eval()
-    return fused_hash_step
+    return took_opt_in
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter,
                                  epilog="--grid {octree,hash} take either --dataset and --fused-step;\n"
-                                        "--grid triplanar implies --dataset mesh and has no fused training step.")
+                                        "--grid triplanar implies --dataset mesh, refuses --fused-step and takes --fused-kernel.")
     ap.add_argument("obj", nargs="?")
     ap.add_argument("--write-test-mesh", metavar="DIR")
     ap.add_argument("--epochs", type=int, default=10)
@@ -107,6 +111,8 @@ def main(argv=None):
     ap.add_argument("--mesh-samples", type=int, default=2_000_000, help="surface samples the occupancy octree is built from")
     ap.add_argument("--batch-size", type=int, default=512)
     ap.add_argument("--fused-step", action="store_true")
+    ap.add_argument("--fused-kernel", action="store_true",
+                    help="--grid triplanar only: train through the kernel-fused step (wisp_triplane_sdf_train_step)")
     ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("W", "H"))
     ap.add_argument("--shading-mode", choices=("rb", "normal", "matcap"), default="normal")
     ap.add_argument("--matcap-path", default=None)
@@ -118,6 +124,8 @@ def main(argv=None):
         if args.fused_step:
             ap.error("--grid triplanar has no fused training step: drop --fused-step")
         args.dataset = "mesh"
+    elif args.fused_kernel:
+        ap.error("--fused-kernel is the triplanar field's fused step: use it with --grid triplanar (--grid hash: --fused-step)")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     from wisp.ops.image import save_u8
     from wisp.trainers import ConfigAdam, ConfigDataloader, ConfigSDFTrainer, SDFTrainer
@@ -143,8 +151,10 @@ def main(argv=None):
     before = trainer.validate()
     metric = next(iter(before))
     t0 = time.time()
-    fused_hash_step = False
-    if args.fused_step:
+    fused_hash_step = fused_triplane_step = False
+    if args.fused_kernel:
+        fused_triplane_step = fit_fused(trainer, ds, cfg, args.device, fused_triplane=True)
+    elif args.fused_step:
         fused_hash_step = fit_fused(trainer, ds, cfg, args.device)
     else:
         trainer.train()
@@ -166,7 +176,7 @@ def main(argv=None):
         vis = renderer.sdf_slice(pipeline.nef, dim=axis)
         save_u8(files[f"slice_{name}"], (np.clip(vis, 0, 1) * 255).round().astype(np.uint8).transpose(1, 0, 2))
     rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, grid=args.grid, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
-               fused_hash_step=fused_hash_step, fused_triplane_eval=fused_triplane_eval,
+               fused_hash_step=fused_hash_step, fused_triplane_eval=fused_triplane_eval, fused_triplane_step=fused_triplane_step,
                metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
                seconds=round(seconds, 3), **{k: os.path.abspath(v) for k, v in files.items()})
     print(json.dumps(rec))
