@@ -1,9 +1,8 @@
 // Field evaluation of the nglod_hash shape as one __device__ function: NeuralSDF over a HashGrid
 // (wisp/models/nefs/neural_sdf.py:120-155 over wisp/models/grids/hash_grid.py:205-233: HashGrid.interpolate 'cat' with the
 // columns from lod_idx * feature_dim on zeroed, or 'sum' over the levels -> [position, features] -> Linear -> relu -> Linear).
-// The hash-grid twin of sdf_eval_point (sdf_eval_dev.h); shared by the three kernels of hash_sdf_eval.hip, so that a value the
-// gradient kernel differences and a distance the marching kernel steps by are bit for bit what the query kernel returns for
-// the same position.
+// This file is the ENCODER half, hash_sdf_point_inputs; the decoder is sdf_decoder_dev.h's, and the two are put together by the
+// kernel bodies of sdf_point_kernels_dev.h (hash_sdf_eval.hip) and sdf_step_dev.h (hash_sdf_train.hip).
 //
 // 16 lanes own one point.  The level columns l * F + k are handed out in adjacent PAIRS (F is even, so a pair lies in one
 // level and in one table row): lane c blends pairs c, c + 16, ... - one corner_setup (hashgrid_dev.h: the cell, the eight
@@ -12,18 +11,16 @@
 // everywhere, a coordinate outside the cube is clamped by corner_setup.  The blend is the forward kernel's: fp32 fma chain
 // over the corners in corner order, rounded through the table dtype as its store does.  'cat' puts the columns behind the
 // position; 'sum' adds the (rounded) levels in level order in fp32 and rounds through the table dtype once, as
-// Tensor.sum(-2) does on a half tensor.  The decoder is that of sdf_eval_point: hidden layer split over the lanes (weights in
-// LDS), fp32 fma chain in input order, the output dot product reduced with four shuffles of width 16.
+// Tensor.sum(-2) does on a half tensor.
 //
 // The end of the file is HOST code: hash_sdf_fill, the shape and pointer checks that fill a HashSdfField.  It lives here, next to the
 // struct it fills, because every entry point over such a field (hash_sdf_eval.hip, hash_sdf_train.hip) runs the same checks.
 #pragma once
 #include "wisp_common.h"
 #include "hashgrid_dev.h"
+#include "sdf_decoder_dev.h"
 
-#define HSDF_GROUP 16
 #define HSDF_MAX_COLS 32
-#define HSDF_MAX_HIDDEN 256
 #define HSDF_MAX_LODS 16
 
 struct HashSdfField {
@@ -31,37 +28,13 @@ struct HashSdfField {
     int64_t begin[HSDF_MAX_LODS + 1];         // first table row of every level, and the number of rows of the whole table
     const void* codebook;                     // MultiTable.feats: [begin[num_lods], feature_dim] of the table dtype
     uint32_t tsize;                           // 2^codebook_bitwidth
-    int num_lods, feature_dim, sum, zero_from_col, cols, hidden;      // cols = decoder feature columns K
-    const float *w1, *b1, *w2, *b2;           // [hidden, 3 + cols], [hidden], [hidden], [1]
+    int num_lods, feature_dim, sum, zero_from_col;
+    SdfDecoder dec;
 };
 
-// LDS of a block: W1 [hidden][in_pad], b1 [hidden], w2 [hidden] | per group: the 3 + cols decoder inputs, then ('sum' only) the
-// num_lods * feature_dim level blends
-struct HashSdfLds { float *w1, *b1, *w2, *in; int in_pad, stride; };
-
-static inline int hash_sdf_in_pad(int cols) { return (3 + cols) | 1; }          // odd row stride: the lanes of a group read different rows
-static inline int hash_sdf_group_floats(int cols, int num_lods, int feature_dim, int sum) {
+// floats of LDS per group: the 3 + cols decoder inputs, then ('sum' only) the num_lods * feature_dim level blends
+constexpr int hash_sdf_group_floats(int cols, int num_lods, int feature_dim, int sum) {
     return 3 + cols + (sum ? num_lods * feature_dim : 0);
-}
-static inline size_t hash_sdf_lds_bytes(int hidden, int cols, int num_lods, int feature_dim, int sum, int groups) {
-    return ((size_t)hidden * hash_sdf_in_pad(cols) + 2 * (size_t)hidden +
-            (size_t)groups * hash_sdf_group_floats(cols, num_lods, feature_dim, sum)) * sizeof(float);
-}
-
-// every thread of the block; ends with the block barrier
-static __device__ __forceinline__ HashSdfLds hash_sdf_stage(float* base, const HashSdfField& fld) {
-    HashSdfLds s;
-    const int in_dim = 3 + fld.cols;
-    s.in_pad = in_dim | 1;
-    s.stride = in_dim + (fld.sum ? fld.num_lods * fld.feature_dim : 0);
-    s.w1 = base;
-    s.b1 = s.w1 + fld.hidden * s.in_pad;
-    s.w2 = s.b1 + fld.hidden;
-    s.in = s.w2 + fld.hidden;
-    for (int e = threadIdx.x; e < fld.hidden * in_dim; e += blockDim.x) s.w1[(e / in_dim) * s.in_pad + e % in_dim] = fld.w1[e];
-    for (int e = threadIdx.x; e < fld.hidden; e += blockDim.x) { s.b1[e] = fld.b1[e]; s.w2[e] = fld.w2[e]; }
-    __syncthreads();
-    return s;
 }
 
 // two adjacent features of one table row (the pair is 2 * sizeof(T) aligned: even column of a row of an even number of features)
@@ -79,24 +52,20 @@ template <> __device__ __forceinline__ void hash_sdf_load_pair<__hip_bfloat16>(c
     a = __uint_as_float(v << 16); b = __uint_as_float(v & 0xffff0000u);
 }
 
-// The two halves of hash_sdf_eval_point below, separate so that the training step (hash_sdf_train.hip) runs the same statements
-// and keeps what its backward needs.  All 16 lanes of a group call them together, with the same position.  c = lane within the
-// group, gin = the group's floats of LDS.  Every rounding is spelled out - explicit fmaf, the compiler's own contraction switched
-// off - for the reason recorded at sdf_eval_coeffs (sdf_eval_dev.h): inlined copies of one function were scheduled differently
-// and returned different bits behind the rounding through a half table dtype.
-//
 // hash_sdf_point_inputs: the decoder inputs [position, features] of one position into gin[0 .. 3 + cols) (and, for 'sum', the level
-// blends behind them).  Ends with the wave barrier that makes them visible to the group.
+// blends behind them).  All 16 lanes of a group call it together, with the same position; c = lane within the group, gin = the
+// group's floats of LDS.  Ends with the wave barrier that makes them visible to the group.  Every rounding is spelled out, as in
+// sdf_decode: here the bits at stake lie behind the rounding through a half table dtype.
 template <typename T>
 static __device__ __forceinline__ void hash_sdf_point_inputs(const HashSdfField& fld, float* gin, int c, float px, float py, float pz) {
 #pragma clang fp contract(off)
     const float pos[3] = {px, py, pz};
     const int F = fld.feature_dim;
     const int level_cols = fld.num_lods * F;
-    float* lev = fld.sum ? gin + 3 + fld.cols : gin + 3;        // 'cat': the level columns ARE the decoder's feature columns
+    float* lev = fld.sum ? gin + 3 + fld.dec.cols : gin + 3;        // 'cat': the level columns ARE the decoder's feature columns
     const T* __restrict__ table = reinterpret_cast<const T*>(fld.codebook);
     __builtin_amdgcn_wave_barrier();                           // the previous evaluation's reads of gin are done
-    for (int q = c; 2 * q < level_cols; q += HSDF_GROUP) {
+    for (int q = c; 2 * q < level_cols; q += SDF_GROUP) {
         const int col = 2 * q;
         const int l = col / F, k = col - l * F;
         float a0 = 0.0f, a1 = 0.0f;
@@ -139,37 +108,14 @@ static __device__ __forceinline__ void hash_sdf_point_inputs(const HashSdfField&
     }
 }
 
-// hash_sdf_decode: the decoder over gin, in = [position, features]; returns the raw output with the bias added.  KEEP (the training
-// step): lane c also leaves, for its hidden units hh = c, c + 16, ..., w2[hh] where the unit is active (0 elsewhere) in ga[hh] and
-// the unit's relu output in gr[hh] - stores only, the arithmetic is the same statements.
-template <bool KEEP>
-static __device__ __forceinline__ float hash_sdf_decode(const HashSdfField& fld, const HashSdfLds& s, const float* gin, int c,
-                                                        float* ga, float* gr) {
-#pragma clang fp contract(off)
-    const int in_dim = 3 + fld.cols;
-    float o = 0.0f;
-    for (int hh = c; hh < fld.hidden; hh += HSDF_GROUP) {
-        const float* wr = s.w1 + hh * s.in_pad;
-        float a = s.b1[hh];
-        for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
-        o = __builtin_fmaf(s.w2[hh], fmaxf(a, 0.0f), o);
-        if (KEEP) {
-            ga[hh] = a > 0.0f ? s.w2[hh] : 0.0f;
-            gr[hh] = fmaxf(a, 0.0f);
-        }
+// the encoder policy of the shared kernel bodies (sdf_point_kernels_dev.h, sdf_step_dev.h)
+template <typename T> struct HashSdfEnc {
+    using Field = HashSdfField;
+    static __host__ __device__ int group_floats(const Field& f) { return hash_sdf_group_floats(f.dec.cols, f.num_lods, f.feature_dim, f.sum); }
+    static __device__ __forceinline__ void point_inputs(const Field& f, float* gin, int c, float px, float py, float pz) {
+        hash_sdf_point_inputs<T>(f, gin, c, px, py, pz);
     }
-#pragma unroll
-    for (int d = HSDF_GROUP / 2; d >= 1; d >>= 1) o += __shfl_xor(o, d, HSDF_GROUP);
-    return o + fld.b2[0];
-}
-
-// A group either runs the whole function or none of it (the shuffles stay inside the group).
-template <typename T>
-static __device__ __forceinline__ float hash_sdf_eval_point(const HashSdfField& fld, const HashSdfLds& s, float* gin, int c,
-                                                            float px, float py, float pz) {
-    hash_sdf_point_inputs<T>(fld, gin, c, px, py, pz);
-    return hash_sdf_decode<false>(fld, s, gin, c, nullptr, nullptr);
-}
+};
 
 // ---------------------------------------------------------------------------------------------------- host side
 // The shape and pointer checks of a hash field, shared by every entry point over it (hash_sdf_eval.hip, hash_sdf_train.hip):
@@ -183,7 +129,7 @@ static inline int hash_sdf_fill(HashSdfField& fld, const char* fn, const void* c
     HSDF_REQUIRE(multiscale == 0 || multiscale == 1, "multiscale must be 0 ('cat') or 1 ('sum')");
     const int cols = multiscale ? feature_dim : num_lods * feature_dim;
     HSDF_REQUIRE(cols <= HSDF_MAX_COLS, "more than 32 feature columns");
-    HSDF_REQUIRE(hidden >= 1 && hidden <= HSDF_MAX_HIDDEN, "hidden width out of range");
+    HSDF_REQUIRE(hidden >= 1 && hidden <= SDF_MAX_HIDDEN, "hidden width out of range");
     HSDF_REQUIRE(codebook_bitwidth >= 1 && codebook_bitwidth <= 30, "codebook_bitwidth out of range");
     HSDF_REQUIRE(zero_from_col >= 0, "zero_from_col is negative");
     HSDF_REQUIRE(dtype == WISP_F32 || dtype == WISP_F16 || dtype == WISP_BF16, "bad dtype");
@@ -200,7 +146,6 @@ static inline int hash_sdf_fill(HashSdfField& fld, const char* fn, const void* c
     for (int l = 0; l <= HSDF_MAX_LODS; ++l) fld.begin[l] = begin_idxes[l <= num_lods ? l : num_lods];
     fld.codebook = codebook; fld.tsize = (uint32_t)tsize;
     fld.num_lods = num_lods; fld.feature_dim = feature_dim; fld.sum = multiscale; fld.zero_from_col = zero_from_col;
-    fld.cols = cols; fld.hidden = hidden;
-    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
+    fld.dec = SdfDecoder{cols, hidden, w1, b1, w2, b2};
     return WISP_OK;
 }

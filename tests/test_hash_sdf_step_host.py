@@ -126,7 +126,7 @@ def test_scratch_bytes_is_monotone_and_rejects_what_the_step_does_not_serve():
 
 
 def step_lds_bytes(hidden, cols, num_lods, F, multi):
-    """the dynamic LDS of hash_sdf_train_kernel (csrc/hash_sdf_train.hip: hst_lds_bytes), restated"""
+    """the dynamic LDS of hash_sdf_train_kernel (csrc/sdf_step_dev.h: sdf_step_lds_bytes over hash_sdf_group_floats), restated"""
     in_dim = 3 + cols
     stage = hidden * (in_dim | 1) + 2 * hidden + 16 * (in_dim + (num_lods * F if multi else 0))
     return 4 * (stage + 16 * (2 * hidden + 2 + cols) + hidden * in_dim + 2 * hidden + 2)

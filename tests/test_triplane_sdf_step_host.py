@@ -240,7 +240,7 @@ def test_scratch_bytes_is_exact_monotone_and_rejects_what_the_step_does_not_serv
 
 
 def step_lds_bytes(hidden, cols):
-    """the dynamic LDS of triplane_sdf_train_kernel (csrc/triplane_sdf_train.hip: tst_lds_bytes), restated"""
+    """the dynamic LDS of triplane_sdf_train_kernel (csrc/sdf_step_dev.h: sdf_step_lds_bytes with 3 + cols floats a group), restated"""
     in_dim = 3 + cols
     stage = hidden * (in_dim | 1) + 2 * hidden + 16 * in_dim
     return 4 * (stage + 16 * (2 * hidden + 2 + cols) + hidden * in_dim + 2 * hidden + 2)
