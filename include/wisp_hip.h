@@ -44,7 +44,8 @@ const char* wisp_last_error(void);
  * wisp_image_field_train_step, wisp_nerf_prune_query, wisp_nerf_prune_query_debug, wisp_nerf_query, wisp_composite_loss_partials, wisp_loss_sum,
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
  * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim, wisp_triplane_sdf_query,
- * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused, wisp_triplane_sdf_train_step - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused, wisp_triplane_sdf_train_step,
+ * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -160,6 +161,27 @@ int wisp_hashgrid_interpolate_bwd_adamw_tail(const float* coords, int64_t n, int
                                              void* bf16_shadow, float lr, float beta1, float beta2, float eps, float weight_decay,
                                              int64_t step, float grad_scale, int64_t* covered_rows /* host */,
                                              const wisp_step_tail* tail, int* tail_done /* host */, wisp_stream_t stream);
+
+/* Either of the two calls above (tail and tail_done both given, or both NULL) with statements of the caller about its buffers:
+ * WISP_HG_BWD_GRAD_CLEAN - grad_codebook is ALL ZERO on entry.  The only writer of the gradient table in front of the reduce launch
+ * is then the emit launch's own atomic fall-back (records past a full slot; indices past the rows their level owns), and the emit
+ * launch puts both on record: a workgroup that owns a bucket and finds neither an overflowed slot of that bucket nor a spill anywhere
+ * in the launch does not touch the gradient of its rows - those rows of grad_codebook are NEITHER READ NOR WRITTEN (they are zero and
+ * stay zero).  A workgroup that finds either reads its rows' gradient, applies it and puts it back to zero as without the flag.
+ * Everything else - the trailing levels, the rows that stay the caller's - is as without the flag, and so is every result, bit for
+ * bit, as long as the statement is true; on a table that is not zero the skipped rows' gradient is ignored and left in place.
+ * WISP_HG_GRAD_CLEAN=0 in the environment makes the library ignore the flag. */
+#define WISP_HG_BWD_GRAD_CLEAN 1u
+int wisp_hashgrid_interpolate_bwd_adamw_flags(const float* coords, int64_t n, int coord_dim,
+                                              const void* grad_feats, int dtype, int feature_dim,
+                                              const int64_t* first_idx, const int32_t* resolutions, int num_lods,
+                                              int codebook_bitwidth, int zero_from_col,
+                                              float* grad_codebook, void* workspace, int64_t workspace_bytes,
+                                              const float* level_cap_scale, float* param, float* exp_avg, float* exp_avg_sq,
+                                              void* bf16_shadow, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                              int64_t step, float grad_scale, int64_t* covered_rows /* host */,
+                                              const wisp_step_tail* tail /* or NULL */, int* tail_done /* host, or NULL */,
+                                              uint32_t flags, wisp_stream_t stream);
 
 /* Diagnostic (no counterpart in the reference's bindings): the integer cell, the position inside it and the 2^d corner rows
  * (relative to the level's first row) that ONE level assigns to every coordinate - the first lines of every reference
@@ -1009,6 +1031,11 @@ int wisp_nerf_step_run(void* step, int slot, const float* gts, const float* next
                        int64_t next_num_rays, uint64_t next_seed, const wisp_nerf_step_hyper* hp,
                        const float* level_cap_scale, void* hashgrid_workspace, int64_t hashgrid_workspace_bytes,
                        int record_timing, int64_t* num_samples, int64_t* covered_rows, float** loss, wisp_stream_t stream);
+/* The caller's statement for the NEXT wisp_nerf_step_run of this handle, and for that call alone (every run forgets it, whatever it
+ * returns): table_grad is all zero on entry - WISP_HG_BWD_GRAD_CLEAN of wisp_hashgrid_interpolate_bwd_adamw_flags, which a run with
+ * hp->optimizer == 2 then passes on.  True right after a successful run with hp->optimizer == 2 on the same buffers when nothing else
+ * has written the gradient since: that run's folded flush and its optimizer launch leave every row of the table gradient at zero. */
+int wisp_nerf_step_grad_clean(void* step);
 /* ms: host f32 [max_steps][4] = hashgrid_fwd, nerf_mlp_fwd, nerf_mlp_bwd, hashgrid_bwd of every timed step since the last read;
  * units: host i64 [max_steps] packed samples of those steps; *num_steps: how many were written.  Resets the record (which holds at
  * most 512 steps: later steps go untimed until it is read). */

@@ -16,6 +16,7 @@
 // double expression, float32 clamp bound, uint32 hash with the reference's primes, float32 blend in corner order).
 #include "wisp_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #include "hashgrid_dev.h"
 #include "step_tail_dev.h"
@@ -392,6 +393,14 @@ hashgrid_bwd_kernel(const float* __restrict__ coords, int64_t n, const T* __rest
 #define HG_FLUSH_PAIRS 1       // (0: A/B builds of the reduce kernel's flush without its 8-byte path, scripts/gpu_r4_k.sh)
 #endif
 
+// Two of the words the emitters write anyway say where their atomic fall-back wrote the gradient table, in bit 31 (no count and no
+// sign-cleared magnitude reaches it): a slot's COUNT word - "this slot overflowed: atomics went to rows of this bucket" - and the
+// workgroup's largest-magnitude word - "a spill index (past the rows its level owns) went to the atomic path: rows of any later
+// level".  A caller that vouches for a zero gradient table (AdamFlush::grad_clean) lets the folded flush leave the table alone
+// wherever neither bit says otherwise.  Every reader of those words masks the bit.
+#define HG_DIRTY_BIT 0x80000000u
+#define HG_WORD_MASK 0x7fffffffu
+
 // Records.  Generic form: { entry inside the bucket, F fp32 gradient values } = 1 + F dwords.  For two features coming
 // from a 16-bit gradient tensor (the bf16 / fp16 training path) the record is packed into TWO dwords: each value keeps
 // sign, exponent and 16 mantissa bits (rounded; 2^-17 relative - the values were products of a 16-bit gradient already)
@@ -456,8 +465,9 @@ hashgrid_bwd_emit_kernel(const float* __restrict__ coords, int64_t n, const T* _
     uint32_t* s_rank = em_smem;                          // [total_ranks] records written so far per (level, bucket)
     uint32_t* s_mx = em_smem + total_ranks;              // largest record magnitude of this workgroup (float bits)
     uint32_t* s_grad = em_smem + total_ranks + 1;        // [EM_TILE][rowp] gradient rows of this tile
+    __shared__ uint32_t s_spill;                         // HG_DIRTY_BIT once a spill index of this workgroup went to the atomic path
     uint32_t mx = 0;
-    if (threadIdx.x == 0) *s_mx = 0;
+    if (threadIdx.x == 0) { *s_mx = 0; s_spill = 0; }
     const int row_dw = num_lods * W;
     const int rowp = row_dw | 1;
     const int lane = threadIdx.x & 63;
@@ -530,6 +540,7 @@ hashgrid_bwd_emit_kernel(const float* __restrict__ coords, int64_t n, const T* _
                 } else {
                     // slot full, or a spill index: the memory-side atomic.  A spill lands where the reference's pointer
                     // arithmetic puts it (rows of the next level, .cu:124-161) unless that is past the whole table.
+                    if (idx >= owned) atomicOr(&s_spill, HG_DIRTY_BIT);        // (rare, off the record path: no flag to carry)
                     const int64_t row = first_idx[l] + (int64_t)idx;
                     if (row < total_rows) {
                         float* p = grad_codebook + row * F;
@@ -542,7 +553,7 @@ hashgrid_bwd_emit_kernel(const float* __restrict__ coords, int64_t n, const T* _
     }
     if (mx) atomicMax(s_mx, mx);
     __syncthreads();
-    if (threadIdx.x == 0) counts[bins.max_base + blockIdx.x] = *s_mx;
+    if (threadIdx.x == 0) counts[bins.max_base + blockIdx.x] = *s_mx | s_spill;          // (the magnitude has its sign bit cleared)
     for (int li = 0; li < levels.n; ++li) {
         const int chunks = bins.chunks[li];
         const uint32_t cap = bins.cap[li];
@@ -550,7 +561,7 @@ hashgrid_bwd_emit_kernel(const float* __restrict__ coords, int64_t n, const T* _
         uint32_t* __restrict__ cnt_l = counts + bins.cnt_base[li];
         for (int b = threadIdx.x; b < chunks; b += EM_THREADS) {
             const uint32_t cn = rank_l[b];
-            cnt_l[(size_t)b * ntiles + blockIdx.x] = cn < cap ? cn : cap;
+            cnt_l[(size_t)b * ntiles + blockIdx.x] = cn <= cap ? cn : (cap | HG_DIRTY_BIT);   // rank cn > cap: records past the slot
         }
     }
 }
@@ -584,8 +595,9 @@ hashgrid_bwd_emit_q_kernel(const float* __restrict__ coords, int64_t n, const T*
     const int total_ranks = bins.rank_base[levels.n];
     uint32_t* s_rank = em_smem;
     uint32_t* s_mx = em_smem + total_ranks;              // largest record magnitude of this workgroup (float bits)
+    __shared__ uint32_t s_spill;                         // HG_DIRTY_BIT once a spill index of this workgroup went to the atomic path
     uint32_t mx = 0;
-    if (threadIdx.x == 0) *s_mx = 0;
+    if (threadIdx.x == 0) { *s_mx = 0; s_spill = 0; }
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     uint32_t* s_queue = em_smem + ((total_ranks + 4) & ~3) + wave * (64 * QROW);
@@ -674,6 +686,7 @@ hashgrid_bwd_emit_q_kernel(const float* __restrict__ coords, int64_t n, const T*
                         } else {
                             // slot full, or a spill index (lands where the reference's pointer arithmetic puts it, .cu:124-161,
                             // unless that is past the whole table)
+                            if (idx >= owned) atomicOr(&s_spill, HG_DIRTY_BIT);        // (rare, off the record path: no flag to carry)
                             const int64_t row = base_l + (int64_t)idx;
                             if (row < total_rows) {
                                 float* pg = grad_codebook + row * F;
@@ -690,7 +703,7 @@ hashgrid_bwd_emit_q_kernel(const float* __restrict__ coords, int64_t n, const T*
     }
     if (mx) atomicMax(s_mx, mx);
     __syncthreads();
-    if (threadIdx.x == 0) counts[bins.max_base + blockIdx.x] = *s_mx;
+    if (threadIdx.x == 0) counts[bins.max_base + blockIdx.x] = *s_mx | s_spill;          // (the magnitude has its sign bit cleared)
     for (int li = 0; li < levels.n; ++li) {
         const int chunks = bins.chunks[li];
         const uint32_t cap = bins.cap[li];
@@ -698,7 +711,7 @@ hashgrid_bwd_emit_q_kernel(const float* __restrict__ coords, int64_t n, const T*
         uint32_t* __restrict__ cnt_l = counts + bins.cnt_base[li];
         for (int b = threadIdx.x; b < chunks; b += THREADS) {
             const uint32_t cn = rank_l[b];
-            cnt_l[(size_t)b * ntiles + blockIdx.x] = cn < cap ? cn : cap;
+            cnt_l[(size_t)b * ntiles + blockIdx.x] = cn <= cap ? cn : (cap | HG_DIRTY_BIT);   // rank cn > cap: records past the slot
         }
     }
 }
@@ -761,9 +774,13 @@ struct AccF32 {             // the non-finite fallback
 // the table (splits == 1) has the slice's complete gradient in LDS - instead of adding it to the gradient table for a separate
 // optimizer pass to read back (and zero), it updates parameters and moments right there.  Pointers are indexed like
 // grad_codebook (table element); shadow = bf16 copy of the parameters, or null.
+// grad_clean: the caller vouches that grad_codebook is all zero on entry (WISP_HG_BWD_GRAD_CLEAN).  What could make a bucket's rows
+// non-zero before its flush is then this launch's own emit fall-back alone, and that is on record (HG_DIRTY_BIT): a bucket workgroup
+// that saw no overflowed slot of its own and no spill in the launch neither reads nor re-zeroes the gradient of its rows.
 struct AdamFlush {
     float* p; float* m; float* v; __hip_bfloat16* shadow;
     float lr, wd, b1, b2, eps, bc1, bc2_sqrt, gscale;
+    int grad_clean;
 };
 // levels [first_level, end_level) of the table that receive no gradient, stepped by `blocks` extra workgroups of the reduce launch
 #define HG_TAIL_ROWS 8192
@@ -781,12 +798,14 @@ struct StepTail {
 };
 static_assert(RD_THREADS == STEP_TAIL_THREADS, "the side jobs run in reduce workgroups");
 
+// may_skip_grad (workgroup-uniform): AdamFlush::grad_clean holds and no emitter reported a spill - whether this bucket's own slots
+// overflowed shows in the walk (s_wave_flag: one word per wave)
 template <typename T, int F, typename ACC, bool ADAM>
 static __device__ __forceinline__ void
 hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, const LevelList& levels, int chunk_shift,
                          const BinLevels& bins, uint32_t ntiles, const uint32_t* __restrict__ counts,
                          const uint32_t* __restrict__ records, float* __restrict__ grad_codebook, int li, int b, int z,
-                         const AdamFlush& ad) {
+                         const AdamFlush& ad, bool may_skip_grad, uint32_t* s_wave_flag) {
     typedef RecordCodec<T, F> Codec;
     constexpr int RW = Codec::RW;
     const int splits = bins.splits[li];
@@ -826,9 +845,12 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
     constexpr int INFLIGHT = 8;
     const uint32_t my_tiles = ntiles > (uint32_t)z ? (ntiles - z + splits - 1) / splits : 0u;   // tiles of this workgroup
     // tile number k of this workgroup goes to wave k % NW, so that all waves have work even when there are few tiles
+    uint32_t seen = 0;                                    // OR of this lane's count words (HG_DIRTY_BIT: a slot overflowed)
     for (uint32_t base = 0; base * NW + wave < my_tiles; base += 64) {
         const uint32_t k = (base + lane) * NW + wave;
-        const uint32_t cnt_of_lane = k < my_tiles ? cnt[z + k * splits] : 0u;
+        const uint32_t cnt_word = k < my_tiles ? cnt[z + k * splits] : 0u;
+        seen |= cnt_word;
+        const uint32_t cnt_of_lane = cnt_word & HG_WORD_MASK;
         const uint32_t cc = (cnt_of_lane + 63u) >> 6;     // chunks of this lane's slot
         uint32_t inc = cc;
 #pragma unroll
@@ -870,7 +892,24 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
             }
         }
     }
+    // the table gradient of this bucket's rows is read (and put back to zero) unless the caller vouched for a zero table and neither
+    // a slot of this bucket nor a spill of the launch says that the emit fall-back wrote it
+    bool need_grad = true;
+    if constexpr (ADAM) {
+        if (may_skip_grad && splits == 1) {
+            const bool overflowed = __ballot((seen & HG_DIRTY_BIT) != 0) != 0ull;
+            if (lane == 0) s_wave_flag[wave] = overflowed ? 1u : 0u;
+        }
+    }
     __syncthreads();
+    if constexpr (ADAM) {
+        if (may_skip_grad && splits == 1) {
+            uint32_t any = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) any |= s_wave_flag[w];
+            need_grad = any != 0;
+        }
+    }
     if (strips) {
         // rows of this bucket: strips of 32 (contiguous 32 * F floats each) spread over the level; addressed from the level's first row
         float* __restrict__ dl = grad_codebook + first_idx[l] * F;
@@ -898,6 +937,10 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
                     }
                     return;
                 }
+                // (one instance with the gradient's loads and one without, chosen per workgroup: a branch around the one load inside the
+                //  loop makes the compiler wait for it alone before it issues the other three)
+                auto flush = [&](auto with_grad) {
+                constexpr bool WITH_GRAD = decltype(with_grad)::value;
                 for (uint32_t i0 = threadIdx.x; i0 < pairs; i0 += PQ * RD_THREADS) {
                     float2 cg[PQ], cp[PQ], cm[PQ], cv[PQ];
                     uint32_t row[PQ];
@@ -905,7 +948,10 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
                     for (int q = 0; q < PQ; ++q) {
                         const uint32_t i = i0 + q * RD_THREADS;
                         row[q] = i < pairs ? bucket_row((uint32_t)b, i, chunk_shift, magic, nbuckets, rot_mask) : 0xffffffffu;
-                        if (row[q] < entries) { cg[q] = pg[row[q]]; cp[q] = pp[row[q]]; cm[q] = pm[row[q]]; cv[q] = pv[row[q]]; }
+                        if (row[q] < entries) {
+                            if constexpr (WITH_GRAD) cg[q] = pg[row[q]]; else cg[q] = make_float2(0.0f, 0.0f);
+                            cp[q] = pp[row[q]]; cm[q] = pm[row[q]]; cv[q] = pv[row[q]];
+                        }
                     }
 #pragma unroll
                     for (int q = 0; q < PQ; ++q) {
@@ -926,6 +972,8 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
                         }
                     }
                 }
+                };
+                if (need_grad) flush(std::true_type{}); else flush(std::false_type{});
                 return;
             }
         }
@@ -976,13 +1024,16 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
             constexpr int PQ = 4;                       // pairs per thread and round trip (8: 99 registers, the same time)
             const uint32_t pairs = lim >> 1;
             if ((lim & 1u) == 0 && (((uintptr_t)dst | (uintptr_t)pp | (uintptr_t)pm | (uintptr_t)pv) & 7u) == 0) {
+                auto flush = [&](auto with_grad) {                      // (two instances: as for the strips above)
+                constexpr bool WITH_GRAD = decltype(with_grad)::value;
                 for (uint32_t i0 = threadIdx.x; i0 < pairs; i0 += PQ * RD_THREADS) {
                     float2 cg[PQ], cp[PQ], cm[PQ], cv[PQ];
 #pragma unroll
                     for (int q = 0; q < PQ; ++q) {
                         const uint32_t i = i0 + q * RD_THREADS;
                         if (i < pairs) {
-                            cg[q] = reinterpret_cast<const float2*>(dst)[i]; cp[q] = reinterpret_cast<const float2*>(pp)[i];
+                            if constexpr (WITH_GRAD) cg[q] = reinterpret_cast<const float2*>(dst)[i]; else cg[q] = make_float2(0.0f, 0.0f);
+                            cp[q] = reinterpret_cast<const float2*>(pp)[i];
                             cm[q] = reinterpret_cast<const float2*>(pm)[i]; cv[q] = reinterpret_cast<const float2*>(pv)[i];
                         }
                     }
@@ -1005,6 +1056,8 @@ hashgrid_bwd_reduce_body(const ACC A, const int64_t* __restrict__ first_idx, con
                         }
                     }
                 }
+                };
+                if (need_grad) flush(std::true_type{}); else flush(std::false_type{});
             } else {
                 for (uint32_t e = threadIdx.x; e < lim; e += RD_THREADS) {
                     const float c = dst[e];
@@ -1125,26 +1178,32 @@ hashgrid_bwd_reduce_kernel(const int64_t* __restrict__ first_idx, LevelList leve
     const int splits = bins.splits[li];
     const int local = bid - bins.blk_base[li];
     const int b = local / splits, z = local - b * splits;
-    // largest record magnitude of the launch (float bits, sign cleared): max over the emitting workgroups' cells
-    uint32_t m = 0;
-    for (uint32_t t = threadIdx.x; t < ntiles; t += RD_THREADS) m = max(m, counts[bins.max_base + t]);
+    // largest record magnitude of the launch (float bits, sign cleared): max over the emitting workgroups' cells; their bit 31
+    // (HG_DIRTY_BIT: a spill index went to the atomic path) rides through the reduction in the same words
+    uint32_t m = 0, spill = 0;
+    for (uint32_t t = threadIdx.x; t < ntiles; t += RD_THREADS) { const uint32_t mw = counts[bins.max_base + t]; m = max(m, mw & HG_WORD_MASK); spill |= mw; }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    if (__ballot((spill & HG_DIRTY_BIT) != 0) != 0ull) m |= HG_DIRTY_BIT;
     if ((threadIdx.x & 63) == 0) s_wave_max[threadIdx.x >> 6] = m;
     __syncthreads();
-    m = s_wave_max[0];
+    m = 0; spill = 0;
 #pragma unroll
-    for (int w = 1; w < RD_THREADS / 64; ++w) m = max(m, s_wave_max[w]);
+    for (int w = 0; w < RD_THREADS / 64; ++w) { const uint32_t x = s_wave_max[w]; m = max(m, x & HG_WORD_MASK); spill |= x & HG_DIRTY_BIT; }
+    const bool may_skip_grad = ADAM && ad.grad_clean != 0 && spill == 0;
+    // (s_wave_max is free from the next barrier on - the body's, behind its zeroing: the body reuses it for the waves' overflow flags)
     const int e = (int)(m >> 23);                          // biased exponent of the largest magnitude (wave- and block-uniform)
     if (e < 255) {
         int sh = 165 - e - extra_bits;                     // see AccFix64; extra_bits: launches of more than 2^21 samples
         if (sh > 159) sh = 159;                            // 2^(sh - 32) must stay a normal float
         AccFix64 A{reinterpret_cast<unsigned long long*>(rd_smem), __uint_as_float((uint32_t)(sh - 32 + 127) << 23),
                    __longlong_as_double((long long)(1023 - sh) << 52)};
-        hashgrid_bwd_reduce_body<T, F, AccFix64, ADAM>(A, first_idx, levels, chunk_shift, bins, ntiles, counts, records, grad_codebook, li, b, z, ad);
+        hashgrid_bwd_reduce_body<T, F, AccFix64, ADAM>(A, first_idx, levels, chunk_shift, bins, ntiles, counts, records, grad_codebook, li, b, z, ad,
+                                                       may_skip_grad, s_wave_max);
     } else {
         AccF32 A{reinterpret_cast<float*>(rd_smem)};
-        hashgrid_bwd_reduce_body<T, F, AccF32, ADAM>(A, first_idx, levels, chunk_shift, bins, ntiles, counts, records, grad_codebook, li, b, z, ad);
+        hashgrid_bwd_reduce_body<T, F, AccF32, ADAM>(A, first_idx, levels, chunk_shift, bins, ntiles, counts, records, grad_codebook, li, b, z, ad,
+                                                     may_skip_grad, s_wave_max);
     }
 }
 
@@ -1205,6 +1264,12 @@ static int64_t queue_emitter_grid_cap(int resident_per_cu) {
 
 // reduce workgroups per coarse level (a level of at most 32 buckets) for a launch of n samples - measured, see bin_plan
 static int64_t coarse_level_wgs(int64_t n) { return n >= ((int64_t)1 << 21) ? 64 : 16; }
+
+// WISP_HG_GRAD_CLEAN=0: a caller's WISP_HG_BWD_GRAD_CLEAN is ignored - every flush reads the gradient table (read at every launch)
+static bool grad_clean_honoured() {
+    const char* e = getenv("WISP_HG_GRAD_CLEAN");
+    return !(e && e[0] == '0');
+}
 
 // bin geometry shared by the workspace query and the launcher
 struct BinPlan { int chunk_shift, max_chunks, max_splits, total_blocks, total_ranks, emit_threads /* queue emitter width, 0 = generic emitter */; int64_t ntiles; BinLevels bins; int64_t count_bytes, record_bytes; bool ok;
@@ -1536,7 +1601,7 @@ static int bwd_adamw_impl(const float* coords, int64_t n, int coord_dim, const v
                           int64_t workspace_bytes, const float* level_cap_scale, float* param,
                           float* exp_avg, float* exp_avg_sq, void* bf16_shadow, float lr, float beta1,
                           float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
-                          int64_t* covered_rows, const StepTail* side_jobs, int* side_done,
+                          int64_t* covered_rows, const StepTail* side_jobs, int* side_done, uint32_t flags,
                           wisp_stream_t stream) {
     WISP_REQUIRE(n >= 0, "negative n");
     WISP_REQUIRE(num_lods >= 1 && num_lods <= HG_MAX_LODS, "num_lods out of range");
@@ -1552,7 +1617,8 @@ static int bwd_adamw_impl(const float* coords, int64_t n, int coord_dim, const v
     WISP_REQUIRE(fill_levels(resolutions, num_lods, coord_dim, tsize, lv) == 0, "bad resolution");
     // bias corrections exactly as wisp_adamw_step_groups computes them
     const AdamFlush ad{param, exp_avg, exp_avg_sq, (__hip_bfloat16*)bf16_shadow, lr, weight_decay, beta1, beta2, eps,
-                       1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step)), grad_scale};
+                       1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step)), grad_scale,
+                       (flags & WISP_HG_BWD_GRAD_CLEAN) != 0 && grad_clean_honoured() ? 1 : 0};
     hipStream_t s = (hipStream_t)stream;
     HG_DISPATCH(launch_bwd, coords, n, grad_feats, first_idx, lv, num_lods, (uint32_t)tsize, zero_from_col,
                 grad_codebook, workspace, workspace_bytes, level_cap_scale, s, &ad, covered_rows, side_jobs, side_done)
@@ -1570,7 +1636,7 @@ extern "C" int wisp_hashgrid_interpolate_bwd_adamw(const float* coords, int64_t 
                                                    int64_t* covered_rows, wisp_stream_t stream) {
     return bwd_adamw_impl(coords, n, coord_dim, grad_feats, dtype, feature_dim, first_idx, resolutions, num_lods, codebook_bitwidth,
                           zero_from_col, grad_codebook, workspace, workspace_bytes, level_cap_scale, param, exp_avg, exp_avg_sq, bf16_shadow,
-                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, nullptr, nullptr, stream);
+                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, nullptr, nullptr, 0u, stream);
 }
 
 // The same with the step's two closing sums riding in the reduce launch (StepTail).  *tail_done (host): 1 when they did; 0 when
@@ -1593,7 +1659,32 @@ extern "C" int wisp_hashgrid_interpolate_bwd_adamw_tail(const float* coords, int
     side.loss_partials = tail->loss_partials; side.loss = tail->loss; side.loss_count = tail->loss_count; side.inv_n = tail->inv_n;
     return bwd_adamw_impl(coords, n, coord_dim, grad_feats, dtype, feature_dim, first_idx, resolutions, num_lods, codebook_bitwidth,
                           zero_from_col, grad_codebook, workspace, workspace_bytes, level_cap_scale, param, exp_avg, exp_avg_sq, bf16_shadow,
-                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, &side, tail_done, stream);
+                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, &side, tail_done, 0u, stream);
+}
+
+// Either of the two calls above - tail and tail_done both given, or both NULL - with the caller's statements about its buffers in
+// `flags`: WISP_HG_BWD_GRAD_CLEAN (see AdamFlush::grad_clean).
+extern "C" int wisp_hashgrid_interpolate_bwd_adamw_flags(const float* coords, int64_t n, int coord_dim, const void* grad_feats,
+                                                         int dtype, int feature_dim, const int64_t* first_idx,
+                                                         const int32_t* resolutions, int num_lods, int codebook_bitwidth,
+                                                         int zero_from_col, float* grad_codebook, void* workspace,
+                                                         int64_t workspace_bytes, const float* level_cap_scale, float* param,
+                                                         float* exp_avg, float* exp_avg_sq, void* bf16_shadow, float lr, float beta1,
+                                                         float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                                                         int64_t* covered_rows, const wisp_step_tail* tail, int* tail_done,
+                                                         uint32_t flags, wisp_stream_t stream) {
+    WISP_REQUIRE((tail == nullptr) == (tail_done == nullptr), "side-job descriptor and its result go together");
+    WISP_REQUIRE((flags & ~(uint32_t)WISP_HG_BWD_GRAD_CLEAN) == 0, "unknown flag");
+    StepTail side{};
+    if (tail) {
+        WISP_REQUIRE(tail->dw_rows >= 0 && tail->loss_count >= 0 && tail->in_dim >= 1 && tail->in_dim <= wisp_mlp::IN, "side-job descriptor out of range");
+        *tail_done = 0;
+        side.dw_partials = tail->dw_partials; side.dec_grad = tail->dec_grad; side.dw_rows = tail->dw_rows; side.in_dim = tail->in_dim;
+        side.loss_partials = tail->loss_partials; side.loss = tail->loss; side.loss_count = tail->loss_count; side.inv_n = tail->inv_n;
+    }
+    return bwd_adamw_impl(coords, n, coord_dim, grad_feats, dtype, feature_dim, first_idx, resolutions, num_lods, codebook_bitwidth,
+                          zero_from_col, grad_codebook, workspace, workspace_bytes, level_cap_scale, param, exp_avg, exp_avg_sq, bf16_shadow,
+                          lr, beta1, beta2, eps, weight_decay, step, grad_scale, covered_rows, tail ? &side : nullptr, tail_done, flags, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- gradient w.r.t. the coordinates
@@ -1878,7 +1969,7 @@ hashgrid_bwd_slot_stats_kernel(LevelList levels, BinLevels bins, uint32_t ntiles
     const uint32_t* __restrict__ c = counts + bins.cnt_base[li];
     const int64_t cells = (int64_t)bins.chunks[li] * ntiles;
     uint32_t m = 0, sum = 0;
-    for (int64_t e = threadIdx.x; e < cells; e += blockDim.x) { const uint32_t v = c[e]; m = max(m, v); sum += v; }
+    for (int64_t e = threadIdx.x; e < cells; e += blockDim.x) { const uint32_t v = c[e] & HG_WORD_MASK; m = max(m, v); sum += v; }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { m = max(m, (uint32_t)__shfl_xor((int)m, d, 64)); sum += (uint32_t)__shfl_xor((int)sum, d, 64); }
     if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = m; s_sum[threadIdx.x >> 6] = sum; }

@@ -104,6 +104,7 @@ struct Step {
     std::vector<hipEvent_t> ev;
     std::vector<int64_t> ev_units;
     int timed_steps = 0;
+    bool grad_clean = false;         // wisp_nerf_step_grad_clean: the caller's statement for the next run, forgotten by every run
 };
 
 template <typename T> static T* at(const Step* s, int64_t off) { return reinterpret_cast<T*>(s->ws + off); }
@@ -215,6 +216,13 @@ extern "C" int wisp_nerf_step_reconfigure(void* step, const wisp_nerf_step_confi
     s->res.assign(cfg->resolutions, cfg->resolutions + cfg->num_lods);
     s->cfg.first_idx_host = s->first_idx_host.data();
     s->cfg.resolutions = s->res.data();
+    s->grad_clean = false;                             // (a statement about the old buffers)
+    return WISP_OK;
+}
+
+extern "C" int wisp_nerf_step_grad_clean(void* step) {
+    WISP_REQUIRE(step, "null handle");
+    static_cast<Step*>(step)->grad_clean = true;
     return WISP_OK;
 }
 
@@ -243,6 +251,8 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
                                   int record_timing, int64_t* num_samples, int64_t* covered_rows, float** loss, wisp_stream_t stream) {
     WISP_REQUIRE(step && (slot == 0 || slot == 1) && gts && hp && num_samples && loss, "null argument");
     Step* s = static_cast<Step*>(step);
+    const uint32_t hg_flags = s->grad_clean ? WISP_HG_BWD_GRAD_CLEAN : 0u;      // for this run alone, however it ends
+    s->grad_clean = false;
     const wisp_nerf_step_config& c = s->cfg;
     MarchSlot& m = s->slot[slot];
     WISP_REQUIRE(m.counted, "this slot holds no counted batch (wisp_nerf_step_count first)");
@@ -346,21 +356,21 @@ extern "C" int wisp_nerf_step_run(void* step, int slot, const float* gts, const 
     NS_MARK(4);                                        // end of the decoder backward = start of the hash-grid backward
     if (tail_fold) {
         int tail_done = 0;
-        NS_CALL(wisp_hashgrid_interpolate_bwd_adamw_tail(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
-                                                         c.num_lods, c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace,
-                                                         hashgrid_workspace_bytes, level_cap_scale, c.table_param, c.table_exp_avg,
-                                                         c.table_exp_avg_sq, c.table_shadow, hp->lr_grid, hp->beta1, hp->beta2, hp->eps,
-                                                         hp->weight_decay, hp->step, hp->grad_scale, covered, &tail, &tail_done, st));
+        NS_CALL(wisp_hashgrid_interpolate_bwd_adamw_flags(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
+                                                          c.num_lods, c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace,
+                                                          hashgrid_workspace_bytes, level_cap_scale, c.table_param, c.table_exp_avg,
+                                                          c.table_exp_avg_sq, c.table_shadow, hp->lr_grid, hp->beta1, hp->beta2, hp->eps,
+                                                          hp->weight_decay, hp->step, hp->grad_scale, covered, &tail, &tail_done, hg_flags, st));
         if (!tail_done) {                              // no binned reduce launch (a tiny batch, a workspace too small): the old launches
             NS_CALL(wisp_nerf_mlp_reduce_partials(tail.dw_partials, tail.dw_rows, tail.in_dim, tail.dec_grad, st));
             NS_CALL(wisp_loss_sum(tail.loss_partials, tail.loss_count, tail.inv_n, tail.loss, st));
         }
     } else if (fold)
-        NS_CALL(wisp_hashgrid_interpolate_bwd_adamw(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
-                                                    c.num_lods, c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace,
-                                                    hashgrid_workspace_bytes, level_cap_scale, c.table_param, c.table_exp_avg,
-                                                    c.table_exp_avg_sq, c.table_shadow, hp->lr_grid, hp->beta1, hp->beta2, hp->eps,
-                                                    hp->weight_decay, hp->step, hp->grad_scale, covered, st));
+        NS_CALL(wisp_hashgrid_interpolate_bwd_adamw_flags(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions,
+                                                          c.num_lods, c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace,
+                                                          hashgrid_workspace_bytes, level_cap_scale, c.table_param, c.table_exp_avg,
+                                                          c.table_exp_avg_sq, c.table_shadow, hp->lr_grid, hp->beta1, hp->beta2, hp->eps,
+                                                          hp->weight_decay, hp->step, hp->grad_scale, covered, nullptr, nullptr, hg_flags, st));
     else
         NS_CALL(wisp_hashgrid_interpolate_bwd(samples, S, 3, g_feats, c.dtype_table, c.feature_dim, c.first_idx, c.resolutions, c.num_lods,
                                               c.bitwidth, c.zero_from_col, c.table_grad, hashgrid_workspace, hashgrid_workspace_bytes,

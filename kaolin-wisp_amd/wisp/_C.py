@@ -38,6 +38,9 @@ SIGNATURES = {
                                             c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp, c_vp],
     "wisp_hashgrid_interpolate_bwd_adamw_tail": [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp,
                                                  c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp],
+    "wisp_hashgrid_interpolate_bwd_adamw_flags": [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp,
+                                                  c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_f32, c_vp, c_vp, c_vp,
+                                                  ctypes.c_uint32, c_vp],
     "wisp_hashgrid_grad_coords": [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp],
     "wisp_hashgrid_bwd_workspace_bytes": [c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp],
     "wisp_hashgrid_bwd_slot_stats": [c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp],
@@ -162,6 +165,7 @@ SIGNATURES = {
     "wisp_nerf_step_reconfigure": [c_vp, c_vp],
     "wisp_nerf_step_destroy": [c_vp],
     "wisp_nerf_step_count": [c_vp, c_i32, c_vp, c_vp, c_i64, c_u64, c_vp],
+    "wisp_nerf_step_grad_clean": [c_vp],
     "wisp_nerf_step_run": [c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp],
     "wisp_nerf_step_read_timing": [c_vp, c_i32, c_vp, c_vp, c_vp],
     "wisp_mesh_to_sdf": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp],
@@ -429,7 +433,8 @@ def hashgrid_interpolate_backward(coords, grad_feats, codebook_shape, first_idx,
     """fp32 grad_codebook - wisp._C.ops.hashgrid_interpolate_backward_cuda (hashgrid_interpolate.cpp:71-105).
     `out` (fp32, same shape) is accumulated into when given.
     adamw (needs `out`): dict(param, exp_avg, exp_avg_sq [fp32, the table's shape], shadow [bf16 or None], lr, beta1, beta2, eps,
-    weight_decay, step, grad_scale) - the table's AdamW step folded into the backward (wisp_hashgrid_interpolate_bwd_adamw);
+    weight_decay, step, grad_scale, grad_clean [optional: `out` is all zero on entry - WISP_HG_BWD_GRAD_CLEAN of include/wisp_hip.h])
+    - the table's AdamW step folded into the backward (wisp_hashgrid_interpolate_bwd_adamw_flags);
     returns (grad, covered) then, covered[l] = leading rows of level l that were updated inside the launch (their gradient is
     not in `out`); all other rows are the caller's to update."""
     coords = _need(coords, torch.float32, "coords")
@@ -463,14 +468,15 @@ def hashgrid_interpolate_backward(coords, grad_feats, codebook_shape, first_idx,
                 assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == grad.numel()
             assert sh is None or (sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() == grad.numel())
             cov = (ctypes.c_int64 * L)()
-            _check(lib.wisp_hashgrid_interpolate_bwd_adamw(_p(coords), n, dim, _p(grad_feats), dt, F,
-                                                           _p(first_idx), res_ptr, L, codebook_bitwidth, zero_from_col, _p(grad),
-                                                           _p(ws), ws.numel() if ws is not None else 0, scale_ptr,
-                                                           _p(prm), _p(m1), _p(m2), _p(sh), float(adamw["lr"]), float(adamw["beta1"]),
-                                                           float(adamw["beta2"]), float(adamw["eps"]), float(adamw["weight_decay"]),
-                                                           int(adamw["step"]), float(adamw.get("grad_scale", 1.0)),
-                                                           ctypes.cast(cov, ctypes.c_void_p), _stream()),
-                   "hashgrid_interpolate_bwd_adamw")
+            _check(lib.wisp_hashgrid_interpolate_bwd_adamw_flags(_p(coords), n, dim, _p(grad_feats), dt, F,
+                                                                 _p(first_idx), res_ptr, L, codebook_bitwidth, zero_from_col, _p(grad),
+                                                                 _p(ws), ws.numel() if ws is not None else 0, scale_ptr,
+                                                                 _p(prm), _p(m1), _p(m2), _p(sh), float(adamw["lr"]), float(adamw["beta1"]),
+                                                                 float(adamw["beta2"]), float(adamw["eps"]), float(adamw["weight_decay"]),
+                                                                 int(adamw["step"]), float(adamw.get("grad_scale", 1.0)),
+                                                                 ctypes.cast(cov, ctypes.c_void_p), None, None,
+                                                                 HG_BWD_GRAD_CLEAN if adamw.get("grad_clean") else 0, _stream()),
+                   "hashgrid_interpolate_bwd_adamw_flags")
             # (levels stepped whole by the launch's tail workgroups report 2^62: rows as THIS table's first_idx spaces them)
             covered = [min(int(c), first_host[l + 1] - first_host[l]) for l, c in enumerate(cov)]
     if fit is not None and ws is not None:
@@ -500,6 +506,7 @@ def hashgrid_grad_coords(coords, grad_feats, codebook, first_idx, resolutions, c
     return out
 
 
+HG_BWD_GRAD_CLEAN = 1                             # include/wisp_hip.h: WISP_HG_BWD_GRAD_CLEAN
 HASHGRID_BWD_WORKSPACE_LIMIT = 24 << 30          # bytes; 288 GB of HBM makes a multi-GB scratch a fair trade
 _bwd_ws = {}
 _slot_fits = {}

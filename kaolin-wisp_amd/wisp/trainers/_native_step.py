@@ -17,6 +17,9 @@ ENABLED = os.environ.get("WISP_NATIVE_STEP", "1") != "0"
 # WISP_STEP_TAIL_FOLD=0: the decoder's dW sum and the loss sum stay launches of their own instead of riding in the hash-grid reduce
 # launch (wisp_nerf_step_hyper.tail_fold; same bits either way)
 TAIL_FOLD = os.environ.get("WISP_STEP_TAIL_FOLD", "1") != "0"
+# WISP_STEP_GRAD_CLEAN=0: no step tells the library that the table gradient is zero on entry (wisp_nerf_step_grad_clean; same bits
+# either way).  Read at every step: A/B runs and tests switch it inside one process.
+grad_clean_enabled = lambda: os.environ.get("WISP_STEP_GRAD_CLEAN", "1") != "0"
 
 
 def _hip():
@@ -50,6 +53,14 @@ class NativeHashStep:
         self.hg_scale = None
         self.fallbacks = 0
         self.steps = 0
+        # The table gradient is known to be all zero: the previous step of this trainer was a native step with the folded optimizer
+        # that succeeded (its flush and its optimizer launch leave every row at zero) and nothing has run since.  The next native
+        # step then says so to the library, whose folded flush leaves the gradient of clean buckets alone.  Cleared by every other
+        # route through MultiviewTrainStep.step / accumulate (`dirty`), by a handle that is rebuilt or pointed at other buffers, and
+        # by the step that uses it.  Code that writes the table's .grad behind the trainer's back must call `dirty()` too.
+        self.grad_clean = False
+        self.rebuilt = False
+        self.clean_steps = 0          # native steps that made the statement
 
     # ------------------------------------------------------------------------------------------------ applicability
     def applies(self, rays, jitter):
@@ -81,6 +92,10 @@ class NativeHashStep:
         blas = grid.blas
         return blas.max_level <= 10 and rays.origins.shape[0] <= t.max_rays and rays.origins.is_contiguous() and rays.dirs.is_contiguous()
 
+    def dirty(self):
+        """something other than a native folded step may have written the table gradient"""
+        self.grad_clean = False
+
     # ------------------------------------------------------------------------------------------------ handle
     def _capacity(self):
         t = self.t
@@ -108,6 +123,7 @@ class NativeHashStep:
                tuple(float(v) for v in tracer._bg_host()), torch.cuda.current_stream().cuda_stream)
         if self.handle is not None and key == self.key:
             return True
+        self.grad_clean, self.rebuilt = False, True   # (other buffers, or a new handle: nothing is known about them)
         level = blas.max_level
         occ = blas._bitfield(level)
         if occ is None:
@@ -217,8 +233,10 @@ class NativeHashStep:
         Python-issued step (buffers too small, empty batch, stale bf16 copy): nothing has been changed then."""
         C = _hip()
         t, d = self.t, self.t._direct
+        clean, self.grad_clean, self.rebuilt = self.grad_clean, False, False   # (whatever happens below: the statement is made once)
         if not self._ensure(rays):
             return None
+        clean = clean and not self.rebuilt and grad_clean_enabled()
         lib, h = C.lib, self.handle
         dev = rays.origins.device
         stream = C._stream()
@@ -252,6 +270,9 @@ class NativeHashStep:
         loss_ptr = ctypes.c_void_p()
         record = 1 if C.TIMING is not None else 0
         t.wait_for_parameters()
+        if clean and hp.optimizer == 2:
+            C._check(lib.wisp_nerf_step_grad_clean(h), "nerf_step_grad_clean")
+            self.clean_steps += 1
         rc = lib.wisp_nerf_step_run(h, slot, gts.data_ptr(),
                                     None if nxt is None else nxt["rays"].origins.data_ptr(), None if nxt is None else nxt["rays"].dirs.data_ptr(),
                                     0 if nxt is None else nxt["rays"].origins.shape[0], 0 if nxt is None else nxt["seed"],
@@ -277,6 +298,7 @@ class NativeHashStep:
             ga, gb = t.flat.ranges["grid"]
             t.fused_elements_last = 2 * sum(max(0, c) for c in cover)
             self.covered_last = cover
+            self.grad_clean = True                    # the flush and the optimizer launch left the whole table gradient at zero
         else:
             t.fused_elements_last = 0
         t.flat.mark_shadow_current()

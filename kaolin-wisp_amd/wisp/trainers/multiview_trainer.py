@@ -891,6 +891,8 @@ class MultiviewTrainStep:
         Call grad_accum_steps - 1 times, then step() with the last micro-batch (set grad_accum_steps first: it is the divisor).
         Returns (loss tensor, num_samples)."""
         assert self.grad_accum_steps > 1, "set grad_accum_steps to the number of micro-batches per optimizer step first"
+        if self._native is not None:
+            self._native.dirty()
         self._refuse_stale_master_forward()
         if self._direct is not None and self.pipeline.nef.training:
             with torch.no_grad():
@@ -923,6 +925,8 @@ class MultiviewTrainStep:
                 loss = done[0]
                 self.calc_adaptive_rays(rays.origins.shape[0])
                 return loss, done[1]
+            if self._native is not None:
+                self._native.dirty()                         # a fall-back, the Python-issued step, the modular step: all write .grad
             if not self._last_step_modular:
                 with torch.no_grad():
                     loss, _ = self._direct.run(rays, img_gts, jitter, prefetch, fused_update=self._fused_update_args())
