@@ -45,7 +45,7 @@ const char* wisp_last_error(void);
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
  * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim, wisp_triplane_sdf_query,
  * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused, wisp_triplane_sdf_train_step,
- * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean, wisp_sdf_lods_train_step - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -424,6 +424,38 @@ int wisp_sdf_tex_train_step(const float* coords, const float* gts, const float* 
                             const float* w1, const float* b1, const float* w2, const float* b2, int hidden,
                             float* const* grad_feats, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, float* loss,
                             void* scratch, int64_t scratch_bytes, void* workspace, int64_t workspace_bytes, wisp_stream_t stream);
+
+/* Both steps with the loss over EVERY level of detail: SDFTrainer.step without only_last (wisp/trainers/sdf_trainer.py:80-123),
+ * which is what lets one trained octree field be evaluated at any lod_idx.  With L = num_lods, k = 0..L-1:
+ *     x_k = [position,] sum_{l <= k} blend_l ;  y_k = decoder(x_k) ;  S_k = sum_s (sdf_k - gt)^2 ;  R_k = sum_s |rgb_k - rgb_gt|^2
+ *     loss = (sum_k w_sdf[k] S_k + sum_k w_rgb[k] R_k) / n
+ * in four launches, all LODs forward and backward in the first.  The reference's loop is w_sdf[k] = 1 and, with sample_tex,
+ * w_rgb[k] = L - k (it adds the RUNNING colour sum to the loss inside the loop, sdf_trainer.py:92-101).
+ * Arguments as for wisp_sdf_tex_train_step, plus:
+ *  n_out 1: a NeuralSDF (rgb_gts and w_rgb NULL, pos_input must be 1, w2 [hidden], b2 [1]); n_out 4: a NeuralSDFTex;
+ *  w_sdf, w_rgb: HOST f32 [num_lods], finite and > 0.  The weight multiplies the constant first, d loss / d sdf_k =
+ *  (2 w_sdf[k]) (sdf_k - gt) / n, so weight 1 leaves the one-LOD statements and their rounding as they are;
+ *  loss f32 [1 + L] (n_out 1) or [1 + 2 L] (n_out 4) is written: loss[0] = total / n, loss[1 + k] = S_k, loss[1 + L + k] = R_k,
+ *  un-normalised; S_{L-1} and R_{L-1} are the tracker's l2_loss / rgb_loss terms.
+ *  channels must be 16, 1 <= hidden <= 256, num_lods <= 16; wisp_sdf_lods_train_scratch_bytes returns -1 for anything else.
+ * Summation orders (all fixed: bitwise repeatable, no float atomics):
+ *  - x_k: the level blends 0..k in level order, from +0 - the one-LOD step's sum over the first k + 1 levels;
+ *  - a workgroup takes floor(16 / L) samples per pass; its rows are q = si L + k (sample-major, LOD-minor).  dW1, db1, dW2, db2
+ *    add the rows of a pass in ascending q, passes in order, then the workgroups: lane r of 16 adds workgroups r, r + 16, ... in
+ *    order and a fixed butterfly adds the 16 lanes;
+ *  - S_k and R_k add the rows of LOD k in sample order; the total adds w_sdf[k] S (one output) or w_rgb[k] R + w_sdf[k] S (four;
+ *    two rounded products, one add) per row in ascending q; then passes and workgroups as above;
+ *  - the gradient of level l's table comes from sum_{k >= l} d loss / d x_k, starting at k = l and adding in ascending k; the
+ *    corner sums over samples are the 64-bit fixed-point sums of wisp_spc_trilinear_multi_bwd, whose scale bounds those SUMS.
+ * With num_lods = 1 and weights 1 the loss and every gradient equal wisp_sdf_train_step's / wisp_sdf_tex_train_step's bit for bit. */
+int64_t wisp_sdf_lods_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int n_out, int pos_input);
+int wisp_sdf_lods_train_step(const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
+                             const int32_t* exsum, const int16_t* points, const int32_t* trinkets, const float* const* feats,
+                             const int32_t* levels, const int64_t* rows, int num_lods, int channels, int half_round, int n_out,
+                             int pos_input, const float* w_sdf, const float* w_rgb, const float* w1, const float* b1,
+                             const float* w2, const float* b2, int hidden, float* const* grad_feats, float* grad_w1, float* grad_b1,
+                             float* grad_w2, float* grad_b2, float* loss, void* scratch, int64_t scratch_bytes, void* workspace,
+                             int64_t workspace_bytes, wisp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Raymarch sample generation  (replace OctreeAS._raymarch_ray / _raymarch_voxel / _raymarch_uniform,

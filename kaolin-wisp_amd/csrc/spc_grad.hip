@@ -1146,3 +1146,321 @@ extern "C" int wisp_sdf_tex_train_step(const float* coords, const float* gts, co
                       half_round, pos_input, w1, b1, w2, b2, hidden, grad_feats, grad_w1, grad_b1, grad_w2, grad_b2, loss, scratch,
                       workspace, workspace_bytes, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------- fused all-LOD SDF regression step
+// The same step with the loss taken over EVERY level of detail (sdf_trainer.py:80-123 without only_last), for the same two fields:
+//     x_k = [position,] sum_{l <= k} blend_l  (the running sum in level order: what the one-LOD step forms on the first k + 1 levels)
+//     y_k = decoder(x_k) ;  S_k = sum_s (sdf_k - gt)^2 ;  R_k = sum_s |rgb_k - rgb_gt|^2
+//     loss = (sum_k w_sdf[k] S_k + sum_k w_rgb[k] R_k) / B
+// sdf_train_kernel gives one 16-lane group to each (sample, level) pair for the lookup and leaves all but 16 / L of them idle
+// through the decoder.  Here the group that looked level k up goes on to run LOD k:
+//   sdf_lods_train_kernel<NOUT>
+//     Phase 1: st_lookup, unchanged.
+//     Phase 2: group (si, k) = row q = si L + k adds the blends 0..k of its sample up in level order from +0, then runs the
+//              statements of sdf_train_kernel's phase 2 on its own rows of the LDS arrays; the loss head scales the constant:
+//              g = (2 w[k]) diff ... / B (w = 1 leaves the one-LOD statements and their rounding as they are).  Lane 0 leaves
+//              S, (R,) and the row's share of the total, T = w_sdf[k] S (one output) or w_rgb[k] R + w_sdf[k] S (four: two rounded
+//              products, one add).  d loss / d x_k, feature columns, goes to LDS.
+//     Phase 3: the owner of an entry adds the rows up in ascending q = si L + k - sample-major, LOD-minor - with the statements of
+//              sdf_train_kernel; S_k and R_k add the rows of LOD k in sample order, the total adds T in ascending q.
+//              Group (si, l) forms the gradient of level l's blend, sum_{k >= l} d loss / d x_k, starting from k = l and adding
+//              in ascending k, and stores it as column block l of dfeat [n][L 16]; the header's magnitude bound is that SUM times
+//              level l's largest corner weight.  The scatter takes the blocks as 'cat' columns (sum = 0).
+//   sdf_lods_train_reduce_kernel   sdf_train_reduce_kernel's sums (lane r adds rows r, r + 16, ... in order, then a fixed
+//              butterfly); loss[0] = total / B, loss[1 + k] = S_k, loss[1 + L + k] = R_k.
+// Every float sum has one of these orders; the table sums are the 64-bit fixed-point ones.  With L = 1 and weights 1 every
+// statement that reaches a result is sdf_train_kernel's, in its order: the results are bitwise equal.
+struct StLodW { float sdf[SG_MAX_LODS], rgb[SG_MAX_LODS]; };
+
+// st_layout's sibling: the partial row has S_k [L] (, R_k [L]) at e_sq and the total at e_tot; the LDS rows of s_sq hold
+// {S, (R,) T}; df [groups][C] is d loss / d x_k of the pass, wt [2][SG_MAX_LODS] the weights
+struct StLodsLayout { int e_b1, e_w2, e_b2, e_sq, e_tot, entries, row_stride, w1, b1, w2, in, ga, r, g, sq, lev, df, wt, own, floats; };
+static __host__ __device__ inline StLodsLayout st_lods_layout(int hidden, int in_dim, int n_out, int num_lods) {
+    StLodsLayout s;
+    s.e_b1 = hidden * in_dim;
+    s.e_w2 = s.e_b1 + hidden;
+    s.e_b2 = s.e_w2 + n_out * hidden;
+    s.e_sq = s.e_b2 + n_out;
+    s.e_tot = s.e_sq + st_n_sq(n_out) * num_lods;
+    s.entries = s.e_tot + 1;
+    s.row_stride = (s.entries + 15) / 16 * 16;
+    s.w1 = 0;
+    s.b1 = s.w1 + hidden * (in_dim | 1);
+    s.w2 = s.b1 + hidden;
+    s.in = s.w2 + n_out * hidden;
+    s.ga = s.in + ST_GROUPS * in_dim;
+    s.r = s.ga + ST_GROUPS * hidden;
+    s.g = s.r + ST_GROUPS * hidden;
+    s.sq = s.g + ST_GROUPS * n_out;
+    s.lev = s.sq + ST_GROUPS * (st_n_sq(n_out) + 1);
+    s.df = s.lev + ST_GROUPS * ST_GROUP;
+    s.wt = s.df + ST_GROUPS * ST_GROUP;
+    s.own = s.wt + 2 * SG_MAX_LODS;
+    s.floats = s.own + s.entries;
+    return s;
+}
+static inline int64_t st_lods_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int in_dim, int n_out) {
+    return (int64_t)st_grid(n, num_lods) * st_lods_layout(hidden, in_dim, n_out, num_lods).row_stride * 4 +
+           sg_round64(n * num_lods * channels * 4) + n * num_lods * 8;
+}
+
+template <int NOUT>
+__global__ void __launch_bounds__(ST_GROUP * ST_GROUPS)
+sdf_lods_train_kernel(const float* __restrict__ coords, const float* __restrict__ gts, const float* __restrict__ rgb_gts /* NOUT == 4 */,
+                      int64_t n, const uint8_t* __restrict__ octree, const int32_t* __restrict__ exsum,
+                      const int16_t* __restrict__ points, const int32_t* __restrict__ trinkets, StField fld, StLodW wt, float inv_batch,
+                      float* __restrict__ partials /* [grid][row] */, float* __restrict__ dfeat /* [n][num_lods][channels] */,
+                      int64_t* __restrict__ chain /* [n][num_lods] */, SgHeader* __restrict__ hdr) {
+#pragma clang fp contract(off)                          // (as in sdf_train_kernel: every fused multiply-add is written as one)
+    static_assert(NOUT == 1 || NOUT == 4, "one output (distance) or four (colour, distance)");
+    constexpr int NSQ = st_n_sq(NOUT), NSQ1 = NSQ + 1;
+    extern __shared__ float s_st[];
+    const int C = fld.channels, H = fld.hidden, NL = fld.num_lods;
+    const int fo = fld.pos_input ? 3 : 0;
+    const int in_dim = fo + C;
+    const int in_pad = in_dim | 1;
+    const int spb = ST_GROUPS / NL;                     // samples per workgroup pass
+    const int nrows = spb * NL;                         // (sample, LOD) rows of a pass; the groups behind them idle
+    const StLodsLayout lay = st_lods_layout(H, in_dim, NOUT, NL);
+    float *s_w1 = s_st + lay.w1, *s_b1 = s_st + lay.b1, *s_w2 = s_st + lay.w2, *s_in = s_st + lay.in, *s_ga = s_st + lay.ga;
+    float *s_r = s_st + lay.r, *s_g = s_st + lay.g, *s_sq = s_st + lay.sq, *s_lev = s_st + lay.lev;
+    float *s_df = s_st + lay.df, *s_wt = s_st + lay.wt, *s_own = s_st + lay.own;
+    for (int e = threadIdx.x; e < H * in_dim; e += blockDim.x) s_w1[(e / in_dim) * in_pad + e % in_dim] = fld.w1[e];
+    for (int e = threadIdx.x; e < H; e += blockDim.x) s_b1[e] = fld.b1[e];
+    for (int e = threadIdx.x; e < NOUT * H; e += blockDim.x) s_w2[e] = fld.w2[e];
+    for (int e = threadIdx.x; e < lay.entries; e += blockDim.x) s_own[e] = 0.0f;
+    if (threadIdx.x < SG_MAX_LODS) { s_wt[threadIdx.x] = wt.sdf[threadIdx.x]; s_wt[SG_MAX_LODS + threadIdx.x] = wt.rgb[threadIdx.x]; }
+    const int c = threadIdx.x & (ST_GROUP - 1);
+    const int grp = threadIdx.x / ST_GROUP;
+    float b2[NOUT];
+    for (int o = 0; o < NOUT; ++o) b2[o] = fld.b2[o];
+    uint32_t mbits = 0;
+    const int my_si = grp / NL, my_li = grp - my_si * NL;                 // this group's (sample of the pass, level = LOD), both phases
+    float* gin = s_in + grp * in_dim;
+    float* ga = s_ga + grp * H;
+    float* gr = s_r + grp * H;
+    __syncthreads();
+    const float two_ws = 2.0f * s_wt[my_li];                              // (2 w) first: exact, and 2 itself for w = 1
+    for (int64_t base = (int64_t)blockIdx.x * spb; base < n; base += (int64_t)gridDim.x * spb) {
+        const int64_t s = base + my_si;
+        const bool live = my_si < spb && s < n;
+        // ---- phase 1: every (sample, level) pair on its own lane group
+        float wm1 = 0.0f;
+        {
+            float acc = 0.0f;
+            if (live) st_lookup(fld, coords, octree, exsum, points, trinkets, s, my_li, c, chain + s * NL + my_li, acc, wm1);
+            s_lev[grp * ST_GROUP + c] = acc;
+        }
+        __syncthreads();
+        // ---- phase 2: the same group runs LOD my_li of its sample on row grp: decoder forward, d loss / d y, decoder backward
+        if (live) {
+            float feat = 0.0f;                                            // channel c, summed over the levels 0..k in order
+            for (int li = 0; li <= my_li; ++li) feat += s_lev[(grp - my_li + li) * ST_GROUP + c];
+            if (c < fo) gin[c] = coords[s * 3 + c];
+            gin[fo + c] = feat;
+        }
+        __builtin_amdgcn_wave_barrier();                 // a group's lanes are in one wave: LDS order suffices
+        if (live) {
+            float out[NOUT] = {};
+            for (int hh = c; hh < H; hh += ST_GROUP) {
+                const float* wr = s_w1 + hh * in_pad;
+                float a = s_b1[hh];
+                for (int i = 0; i < in_dim; ++i) a = __builtin_fmaf(wr[i], gin[i], a);
+                const float r = fmaxf(a, 0.0f);
+                for (int o = 0; o < NOUT; ++o) out[o] = __builtin_fmaf(s_w2[o * H + hh], r, out[o]);
+                ga[hh] = a > 0.0f ? 1.0f : 0.0f;        // the relu mask; finished below
+                gr[hh] = r;
+            }
+#pragma unroll
+            for (int d = ST_GROUP / 2; d >= 1; d >>= 1)
+                for (int o = 0; o < NOUT; ++o) out[o] += __shfl_xor(out[o], d, ST_GROUP);
+            // ---- the loss head of sdf_train_kernel with the LOD's weights
+            float g[NOUT], sq[NSQ1];
+            const float dd = (out[NOUT - 1] + b2[NOUT - 1]) - gts[s];
+            g[NOUT - 1] = two_ws * dd * inv_batch;
+            sq[0] = dd * dd;
+            if constexpr (NOUT == 4) {
+                const float two_wc = 2.0f * s_wt[SG_MAX_LODS + my_li];
+                float d[3];
+                for (int o = 0; o < 3; ++o) {
+                    const float co = 1.0f / (1.0f + expf(-(out[o] + b2[o])));
+                    d[o] = co - rgb_gts[s * 3 + o];
+                    g[o] = two_wc * d[o] * (co * (1.0f - co)) * inv_batch;
+                }
+                sq[1] = __builtin_fmaf(d[1], d[1], d[0] * d[0]) + d[2] * d[2];
+                sq[2] = s_wt[SG_MAX_LODS + my_li] * sq[1] + s_wt[my_li] * sq[0];      // colour + distance, in that order
+            } else {
+                sq[1] = s_wt[my_li] * sq[0];
+            }
+            // ---- end of the loss head
+            for (int hh = c; hh < H; hh += ST_GROUP) {
+                float t = NOUT == 1 ? s_w2[hh] * g[0] : __builtin_fmaf(s_w2[hh], g[0], 0.0f);         // rounding: as sdf_train_kernel
+                for (int o = 1; o < NOUT; ++o) t = __builtin_fmaf(s_w2[o * H + hh], g[o], t);
+                ga[hh] = ga[hh] != 0.0f ? t : 0.0f;     // the relu's backward selects
+                if constexpr (NOUT == 1) gr[hh] *= g[0];
+            }
+            if (c == 0) {
+                for (int o = 0; o < NOUT; ++o) s_g[grp * NOUT + o] = g[o];
+                for (int k = 0; k < NSQ1; ++k) s_sq[grp * NSQ1 + k] = sq[k];
+            }
+        } else if (grp < nrows) {
+            for (int hh = c; hh < H; hh += ST_GROUP) { ga[hh] = 0.0f; gr[hh] = 0.0f; }
+            if (c < fo) gin[c] = 0.0f;
+            gin[fo + c] = 0.0f;
+            if (c < NOUT) s_g[grp * NOUT + c] = 0.0f;
+            if (c < NSQ1) s_sq[grp * NSQ1 + c] = 0.0f;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (live) {
+            float dx = 0.0f;                                              // d loss / d x_k, feature columns only
+            for (int hh = 0; hh < H; ++hh) dx = __builtin_fmaf(ga[hh], s_w1[hh * in_pad + fo + c], dx);
+            s_df[grp * ST_GROUP + c] = dx;
+        }
+        __syncthreads();
+        // ---- the gradient of level l's blend: every LOD from l on saw it; from k = l, ascending k
+        if (live) {
+            float suf = s_df[grp * ST_GROUP + c];
+            for (int k = my_li + 1; k < NL; ++k) suf += s_df[(grp - my_li + k) * ST_GROUP + c];
+            dfeat[(s * NL + my_li) * C + c] = suf;
+            const uint32_t b = __float_as_uint(wm1 * fabsf(suf)) & 0x7fffffffu;
+            const uint32_t nb = (!(suf == suf) || !(wm1 == wm1)) ? 0x7fc00000u : b;
+            mbits = nb > mbits ? nb : mbits;
+        }
+        // ---- phase 3: the thread that owns an entry adds the rows up in ascending q = si L + k
+        for (int e = threadIdx.x; e < lay.entries; e += blockDim.x) {
+            float acc = 0.0f;
+            if (e < lay.e_b1) {
+                const int hh = e / in_dim, i = e - hh * in_dim;
+                for (int q = 0; q < nrows; ++q) acc = __builtin_fmaf(s_ga[q * H + hh], s_in[q * in_dim + i], acc);
+            } else if (e < lay.e_w2) {
+                const int hh = e - lay.e_b1;
+                for (int q = 0; q < nrows; ++q) acc += s_ga[q * H + hh];
+            } else if (e < lay.e_b2) {
+                const int o = NOUT == 1 ? 0 : (e - lay.e_w2) / H, hh = (e - lay.e_w2) - o * H;        // rounding: as sdf_train_kernel
+                for (int q = 0; q < nrows; ++q)
+                    acc = NOUT == 1 ? acc + s_r[q * H + hh] : __builtin_fmaf(s_g[q * NOUT + o], s_r[q * H + hh], acc);
+            } else if (e < lay.e_sq) {
+                for (int q = 0; q < nrows; ++q) acc += s_g[q * NOUT + (e - lay.e_b2)];
+            } else if (e < lay.e_tot) {                                   // S_k, then R_k: the rows of LOD k in sample order
+                const int j = (e - lay.e_sq) / NL, k = (e - lay.e_sq) - j * NL;
+                for (int si = 0; si < spb; ++si) acc += s_sq[(si * NL + k) * NSQ1 + j];
+            } else {
+                for (int q = 0; q < nrows; ++q) acc += s_sq[q * NSQ1 + NSQ];
+            }
+            s_own[e] += acc;
+        }
+        __syncthreads();
+    }
+    for (int e = threadIdx.x; e < lay.entries; e += blockDim.x) partials[(int64_t)blockIdx.x * lay.row_stride + e] = s_own[e];
+    mbits = sg_wave_umax(mbits);
+    if ((threadIdx.x & 63) == 0 && mbits > __atomic_load_n(&hdr->absmax_bits, __ATOMIC_RELAXED)) atomicMax(&hdr->absmax_bits, mbits);
+}
+
+__global__ void __launch_bounds__(256)
+sdf_lods_train_reduce_kernel(const float* __restrict__ partials, int rows, int H, int in_dim, int n_out, int num_lods,
+                             float* __restrict__ gw1, float* __restrict__ gb1, float* __restrict__ gw2, float* __restrict__ gb2,
+                             float* __restrict__ loss, float inv_batch) {
+    // sdf_train_reduce_kernel over the all-LOD row: 16 lanes per entry, lane r adds rows r, r + 16, ... in order, then a butterfly
+    const StLodsLayout lay = st_lods_layout(H, in_dim, n_out, num_lods);
+    const int r0 = threadIdx.x & 15;
+    for (int e = blockIdx.x * 16 + (threadIdx.x >> 4); e < lay.entries + 15; e += gridDim.x * 16) {
+        const bool in = e < lay.entries;
+        float acc = 0.0f;
+        if (in)
+            for (int r = r0; r < rows; r += 16) acc += partials[(int64_t)r * lay.row_stride + e];
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 16);
+        if (!in || r0 != 0) continue;
+        if (e < lay.e_b1) gw1[e] += acc;
+        else if (e < lay.e_w2) gb1[e - lay.e_b1] += acc;
+        else if (e < lay.e_b2) gw2[e - lay.e_w2] += acc;
+        else if (e < lay.e_sq) gb2[e - lay.e_b2] += acc;
+        else if (e == lay.e_tot) loss[0] = acc * inv_batch;
+        else loss[1 + (e - lay.e_sq)] = acc;            // S_k at 1 + k, R_k at 1 + L + k, un-normalised
+    }
+}
+
+template <int NOUT>
+static int st_lods_step(const char* who, const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
+                        const int32_t* exsum, const int16_t* points, const int32_t* trinkets, const float* const* feats,
+                        const int32_t* levels, const int64_t* rows, int num_lods, int channels, int half_round, int pos_input,
+                        const float* w_sdf, const float* w_rgb, const float* w1, const float* b1, const float* w2, const float* b2,
+                        int hidden, float* const* grad_feats, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
+                        float* loss, void* scratch, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    StField fld;
+    StLodW wt;
+    SgLods ml;
+    if (sg_fill(ml, levels, rows, num_lods) != 0) return wisp_fail(WISP_ERR_INVALID, who, "bad level or row count");
+    for (int l = 0; l < SG_MAX_LODS; ++l) { wt.sdf[l] = 1.0f; wt.rgb[l] = 1.0f; }
+    for (int l = 0; l < num_lods; ++l) {
+        if (!(feats[l] && grad_feats[l] && (l == 0 || levels[l] > levels[l - 1]))) return wisp_fail(WISP_ERR_INVALID, who, "bad level list");
+        fld.feats[l] = feats[l]; fld.level[l] = levels[l]; ml.grad[l] = grad_feats[l];
+        wt.sdf[l] = w_sdf[l];
+        if (NOUT == 4) wt.rgb[l] = w_rgb[l];
+        if (!(std::isfinite(wt.sdf[l]) && wt.sdf[l] > 0.0f && std::isfinite(wt.rgb[l]) && wt.rgb[l] > 0.0f))
+            return wisp_fail(WISP_ERR_INVALID, who, "the LOD weights must be finite and > 0");
+    }
+    fld.num_lods = num_lods; fld.channels = channels; fld.half_round = half_round; fld.hidden = hidden;
+    fld.max_level = levels[num_lods - 1]; fld.pos_input = pos_input;
+    fld.w1 = w1; fld.b1 = b1; fld.w2 = w2; fld.b2 = b2;
+    const SgPlan pl = sg_plan(ml.base[num_lods], channels, 0);
+    if (workspace_bytes < pl.bytes) return wisp_fail(WISP_ERR_INVALID, who, "workspace too small (wisp_spc_bwd_workspace_bytes)");
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    SgHeader* hdr = reinterpret_cast<SgHeader*>(ws);
+    const int in_dim = (pos_input ? 3 : 0) + channels;
+    const int grid = st_grid(n, num_lods);
+    const StLodsLayout lay = st_lods_layout(hidden, in_dim, NOUT, num_lods);
+    float* partials = static_cast<float*>(scratch);
+    float* dfeat = partials + (size_t)grid * lay.row_stride;
+    int64_t* chain = reinterpret_cast<int64_t*>(reinterpret_cast<unsigned char*>(dfeat) + sg_round64(n * num_lods * channels * 4));
+    const size_t lds = (size_t)lay.floats * sizeof(float);
+    const float inv_batch = 1.0f / (float)n;
+    if (hipMemsetAsync(hdr, 0, sizeof(SgHeader), s) != hipSuccess) return wisp_fail(WISP_ERR_LAUNCH, who, "hipMemsetAsync failed");
+    if (const hipError_t e = WISP_ALLOW_LDS(sdf_lods_train_kernel<NOUT>, lds)) return wisp_fail(WISP_ERR_LAUNCH, who, hipGetErrorString(e));
+    hipLaunchKernelGGL(sdf_lods_train_kernel<NOUT>, dim3(grid), dim3(ST_GROUP * ST_GROUPS), lds, s, coords, gts, rgb_gts, n, octree,
+                       exsum, points, trinkets, fld, wt, inv_batch, partials, dfeat, chain, hdr);
+    hipLaunchKernelGGL(sdf_lods_train_reduce_kernel, dim3((lay.entries + 15) / 16), dim3(256), 0, s, partials, grid, hidden, in_dim,
+                       NOUT, num_lods, grad_w1, grad_b1, grad_w2, grad_b2, loss, inv_batch);
+    // the corner sums: one column block per level ('cat' columns, sum = 0); the magnitude bound is in the header already
+    const SgCall c{coords, chain, 1, num_lods, 1, points, trinkets, dfeat, n, num_lods, channels, 0, channels};
+    sg_scatter(c, ml, pl, ws, s, true);
+    sg_finalize(c, ml, pl, ws, s);
+    if (const hipError_t e = hipGetLastError()) return wisp_fail(WISP_ERR_LAUNCH, who, hipGetErrorString(e));
+    return WISP_OK;
+}
+
+extern "C" int64_t wisp_sdf_lods_train_scratch_bytes(int64_t n, int num_lods, int channels, int hidden, int n_out, int pos_input) {
+    if (n < 0 || num_lods < 1 || num_lods > SG_MAX_LODS || channels != ST_GROUP || hidden < 1 || hidden > ST_MAX_HIDDEN ||
+        (n_out != 1 && n_out != 4) || (pos_input != 0 && pos_input != 1) || (n_out == 1 && pos_input != 1))
+        return -1;
+    return st_lods_scratch_bytes(n, num_lods, channels, hidden, (pos_input ? 3 : 0) + channels, n_out);
+}
+
+extern "C" int wisp_sdf_lods_train_step(const float* coords, const float* gts, const float* rgb_gts, int64_t n, const uint8_t* octree,
+                                        const int32_t* exsum, const int16_t* points, const int32_t* trinkets,
+                                        const float* const* feats, const int32_t* levels, const int64_t* rows, int num_lods,
+                                        int channels, int half_round, int n_out, int pos_input, const float* w_sdf,
+                                        const float* w_rgb, const float* w1, const float* b1, const float* w2, const float* b2,
+                                        int hidden, float* const* grad_feats, float* grad_w1, float* grad_b1, float* grad_w2,
+                                        float* grad_b2, float* loss, void* scratch, int64_t scratch_bytes, void* workspace,
+                                        int64_t workspace_bytes, wisp_stream_t stream) {
+    WISP_REQUIRE(n >= 1 && num_lods >= 1 && num_lods <= SG_MAX_LODS, "bad sizes");
+    WISP_REQUIRE(channels == ST_GROUP, "the fused all-LOD SDF step is built for 16 feature channels (nglod_octree.yaml)");
+    WISP_REQUIRE(hidden >= 1 && hidden <= ST_MAX_HIDDEN, "hidden width out of range");
+    WISP_REQUIRE(n_out == 1 || n_out == 4, "n_out must be 1 or 4");
+    WISP_REQUIRE(pos_input == 0 || pos_input == 1, "pos_input must be 0 or 1");
+    WISP_REQUIRE(n_out == 4 || pos_input == 1, "a one-output field takes the position (pos_input must be 1)");
+    WISP_REQUIRE(coords && gts && octree && exsum && points && trinkets && feats && levels && rows && w_sdf && w1 && b1 && w2 && b2 &&
+                 grad_feats && grad_w1 && grad_b1 && grad_w2 && grad_b2 && loss && scratch && workspace, "null pointer");
+    WISP_REQUIRE((n_out == 4) == (rgb_gts != nullptr) && (n_out == 4) == (w_rgb != nullptr),
+                 "rgb_gts and w_rgb go with four outputs and with them only");
+    WISP_REQUIRE(scratch_bytes >= wisp_sdf_lods_train_scratch_bytes(n, num_lods, channels, hidden, n_out, pos_input),
+                 "scratch too small (wisp_sdf_lods_train_scratch_bytes)");
+    if (n_out == 1)
+        return st_lods_step<1>(__func__, coords, gts, nullptr, n, octree, exsum, points, trinkets, feats, levels, rows, num_lods,
+                               channels, half_round, 1, w_sdf, nullptr, w1, b1, w2, b2, hidden, grad_feats, grad_w1, grad_b1, grad_w2,
+                               grad_b2, loss, scratch, workspace, workspace_bytes, (hipStream_t)stream);
+    return st_lods_step<4>(__func__, coords, gts, rgb_gts, n, octree, exsum, points, trinkets, feats, levels, rows, num_lods, channels,
+                           half_round, pos_input, w_sdf, w_rgb, w1, b1, w2, b2, hidden, grad_feats, grad_w1, grad_b1, grad_w2, grad_b2,
+                           loss, scratch, workspace, workspace_bytes, (hipStream_t)stream);
+}

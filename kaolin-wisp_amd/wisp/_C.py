@@ -113,6 +113,9 @@ SIGNATURES = {
     "wisp_sdf_tex_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32, c_i32],
     "wisp_sdf_tex_train_step": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp,
                                 c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "wisp_sdf_lods_train_scratch_bytes": [c_i64, c_i32, c_i32, c_i32, c_i32, c_i32],
+    "wisp_sdf_lods_train_step": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "wisp_grid_interpolate_fwd": [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp],
     "wisp_grid_interpolate_bwd": [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp],
     "wisp_small_decoder_fwd": [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -187,7 +190,7 @@ SIGNATURES = {
     "wisp_last_error": [],
     "wisp_abi_version": [],
 }
-_RESTYPES = {"wisp_ssim_scratch_bytes": c_i64, "wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_triplane_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
+_RESTYPES = {"wisp_ssim_scratch_bytes": c_i64, "wisp_image_field_render_partials": c_i64, "wisp_image_field_train_scratch_bytes": c_i64, "wisp_mesh_sdf_workspace_bytes": c_i64, "wisp_nerf_mlp_bwd_workspace_bytes": c_i64, "wisp_spc_bwd_workspace_bytes": c_i64, "wisp_sdf_train_scratch_bytes": c_i64, "wisp_sdf_tex_train_scratch_bytes": c_i64, "wisp_sdf_lods_train_scratch_bytes": c_i64, "wisp_hash_sdf_train_scratch_bytes": c_i64, "wisp_triplane_sdf_train_scratch_bytes": c_i64, "wisp_hashgrid_bwd_workspace_bytes": c_i64, "wisp_scan_workspace_bytes": c_i64, "wisp_nerf_mlp_param_count": c_i64, "wisp_nerf_mlp_workspace_floats": c_i64,
              "wisp_last_error": ctypes.c_char_p, "wisp_host_reader_create": c_vp, "wisp_host_reader_destroy": None,
              "wisp_nerf_step_config_bytes": c_i64, "wisp_nerf_step_workspace_bytes": c_i64, "wisp_nerf_step_create": c_vp,
              "wisp_nerf_step_destroy": None}
@@ -1609,6 +1612,55 @@ def sdf_tex_train_step(coords, gts, rgb, octree, exsum, points, trinkets, feats,
                                        _p(w1), _p(b1), _p(w2), _p(b2), H, gptr, _p(grad_w1), _p(grad_b1), _p(grad_w2), _p(grad_b2),
                                        _p(loss), _p(scratch), scratch.numel(), _p(ws), ws.numel(), _stream()),
            "sdf_tex_train_step")
+    return loss
+
+
+def sdf_lods_train_step(coords, gts, rgb, octree, exsum, points, trinkets, feats, levels, half_round, pos_input, w_sdf, w_rgb, w1, b1,
+                        w2, b2, grad_feats, grad_w1, grad_b1, grad_w2, grad_b2):
+    """Forward + loss + backward of one SDF regression step with the loss over every LOD (wisp_sdf_lods_train_step): coords [n,3],
+    gts [n,1]; rgb None (a NeuralSDF: w2 [1,H] or [H], b2 [1], pos_input 1) or [n,3] (a NeuralSDFTex: w2 [4,H], b2 [4]); w_sdf /
+    w_rgb: one positive weight per LOD (w_rgb None without colours) -> f32 [1 + L] or [1 + 2L] = {sum_k (w_sdf[k] S_k + w_rgb[k]
+    R_k) / n, S_0..S_{L-1}, R_0..R_{L-1}} with the un-normalised squared-error sums of LOD k; the gradients are ADDED to
+    grad_feats (list, one per level) and grad_w1 / b1 / w2 / b2."""
+    coords = _need(coords, torch.float32, "coords")
+    gts = _need(gts, torch.float32, "gts").reshape(-1)
+    n, L, C, H = coords.shape[0], len(feats), feats[0].shape[1], w1.shape[0]
+    dev = coords.device
+    n_out = 1 if rgb is None else 4
+    pos_input = int(bool(pos_input))
+    if rgb is not None:
+        rgb = _need(rgb, torch.float32, "rgb")
+        assert tuple(rgb.shape) == (n, 3) and rgb.is_contiguous()
+    assert (w_rgb is None) == (rgb is None) and len(w_sdf) == L and (w_rgb is None or len(w_rgb) == L)
+    assert gts.shape[0] == n
+    assert all(f.dtype == torch.float32 and f.is_contiguous() and f.shape[1] == C for f in feats)
+    assert all(g.dtype == torch.float32 and g.is_contiguous() and g.shape == f.shape for g, f in zip(grad_feats, feats))
+    for a in (w1, b1, w2, b2, grad_w1, grad_b1, grad_w2, grad_b2):
+        assert a.device == dev and a.dtype == torch.float32 and a.is_contiguous()
+    assert all(f.device == dev for f in feats) and all(g.device == dev for g in grad_feats)
+    assert tuple(w1.shape) == (H, 3 * pos_input + C) and w2.numel() == n_out * H and b1.numel() == H and b2.numel() == n_out
+    assert tuple(grad_w1.shape) == tuple(w1.shape) and grad_w2.numel() == n_out * H and grad_b1.numel() == H and grad_b2.numel() == n_out
+    need = int(lib.wisp_sdf_lods_train_scratch_bytes(n, L, C, H, n_out, pos_input))
+    if need < 0:
+        raise RuntimeError(f"sdf_lods_train_step: unsupported shape (lods {L}, channels {C}, hidden {H}, outputs {n_out}, "
+                           f"pos_input {pos_input})")
+    scratch = _sdf_scratch.get(dev, need)
+    rarr, rptr = _host_i64([f.shape[0] for f in feats])
+    ws = _spc_bwd_workspace(dev, int(rarr.sum()), C)
+    farr, fptr = _ptr_array(feats)
+    garr, gptr = _ptr_array(grad_feats)
+    larr, lptr = _host_i32(levels)
+    wsdf = (ctypes.c_float * L)(*[float(w) for w in w_sdf])
+    wrgb = (ctypes.c_float * L)(*[float(w) for w in w_rgb]) if w_rgb is not None else None
+    loss = torch.empty(1 + (1 if rgb is None else 2) * L, dtype=torch.float32, device=dev)
+    _check(lib.wisp_sdf_lods_train_step(_p(coords), _p(gts), _p(rgb) if rgb is not None else None, n,
+                                        _p(_need(octree, torch.uint8, "octree")), _p(_need(exsum, torch.int32, "exsum")),
+                                        _p(_need(points, torch.int16, "points")), _p(_need(trinkets, torch.int32, "trinkets")), fptr,
+                                        lptr, rptr, L, C, int(half_round), n_out, pos_input, ctypes.cast(wsdf, c_vp),
+                                        ctypes.cast(wrgb, c_vp) if wrgb is not None else None, _p(w1), _p(b1), _p(w2), _p(b2), H, gptr,
+                                        _p(grad_w1), _p(grad_b1), _p(grad_w2), _p(grad_b2), _p(loss), _p(scratch), scratch.numel(),
+                                        _p(ws), ws.numel(), _stream()),
+           "sdf_lods_train_step")
     return loss
 
 

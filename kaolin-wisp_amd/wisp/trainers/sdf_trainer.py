@@ -25,13 +25,16 @@ def _hip():
 
 class SDFTrainStep:
     def __init__(self, nef, lr=1e-3, eps=1e-15, weight_decay=0.0, grid_lr_weight=1.0, betas=(0.9, 0.999), optimizer='adam',
-                 only_last=True, alpha=0.99, momentum=0.0, fused_hash=False, fused_triplane=False):
+                 only_last=True, alpha=0.99, momentum=0.0, fused_hash=False, fused_triplane=False, fused_lods=False):
         self.nef = nef
         # opt-in: a NeuralSDF over a HashGrid trains through wisp_hash_sdf_train_step (see _fused_field); a trainer built without
         # it keeps the modular launches over a hash grid, with the results it always had
         self.fused_hash = bool(fused_hash)
         # opt-in, likewise: a NeuralSDF over a TriplanarGrid trains through wisp_triplane_sdf_train_step
         self.fused_triplane = bool(fused_triplane)
+        # opt-in, likewise: with only_last=False a NeuralSDF / NeuralSDFTex over an OctreeGrid trains through
+        # wisp_sdf_lods_train_step, the loss over every LOD in one launch; without it only_last=False keeps the modular launches
+        self.fused_lods = bool(fused_lods)
         self.flat = FlatParams(nef)
         self.lr, self.eps, self.weight_decay, self.grid_lr_weight, self.betas = lr, eps, weight_decay, grid_lr_weight, betas
         self.optimizer = str(optimizer).lower()
@@ -71,7 +74,9 @@ class SDFTrainStep:
         of them) gets what wisp_sdf_tex_train_step needs under the same gates.  A plain NeuralSDF over a HashGrid gets what
         wisp_hash_sdf_train_step needs (_fused_field_hash) - only in a trainer built with fused_hash=True; one over a TriplanarGrid
         what wisp_triplane_sdf_train_step needs (_fused_field_triplane) - only in a trainer built with fused_triplane=True.
-        WISP_SDF_TRAIN_FUSED=0 keeps the modular launches."""
+        With only_last=False, the loss over every LOD, the two octree fields get what wisp_sdf_lods_train_step needs - the same
+        gates, the cache entry marked lods_loss=True - only in a trainer built with fused_lods=True; every other field, and every
+        trainer without that flag, then keeps the modular launches.  WISP_SDF_TRAIN_FUSED=0 keeps the modular launches."""
         import os
         if getattr(self, "_fused_seen_only_last", None) != self.only_last:        # toggled since the decision was taken
             self._fused_cache, self._fused_seen_only_last = None, self.only_last
@@ -84,13 +89,16 @@ class SDFTrainStep:
             else:
                 return cached or None
         self._fused_cache = False
-        if os.environ.get("WISP_SDF_TRAIN_FUSED", "1") == "0" or not self.only_last:
+        all_lods = not self.only_last
+        if os.environ.get("WISP_SDF_TRAIN_FUSED", "1") == "0" or (all_lods and not getattr(self, "fused_lods", False)):
             return None
         from wisp.accelstructs import OctreeAS
         from wisp.models.grids import HashGrid, OctreeGrid, TriplanarGrid
         from wisp.models.nefs._grid_mlp import _fusable_small_decoder
         nef = self.nef
         grid, dec = getattr(nef, "grid", None), getattr(nef, "decoder", None)
+        if all_lods and type(grid) is not OctreeGrid:             # the all-LOD step exists for the octree fields only
+            return None
         if type(grid) is HashGrid:
             return self._fused_field_hash(grid, dec) if self.fused_hash and dec is not None else None
         if type(grid) is TriplanarGrid:
@@ -110,7 +118,7 @@ class SDFTrainStep:
         if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.grad is not None and q.grad.is_contiguous()
                    and q.grad.dtype == torch.float32 for q in prm):
             return None
-        self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm)
+        self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm, lods_loss=all_lods)
         return self._fused_cache
 
     def _fused_field_tex(self, grid, dec):
@@ -141,7 +149,7 @@ class SDFTrainStep:
         if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.grad is not None and q.grad.is_contiguous()
                    and q.grad.dtype == torch.float32 for q in prm):
             return None
-        self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm, tex=True, pos=pos)
+        self._fused_cache = dict(grid=grid, dec=dec, lods=grid.num_lods, prm=prm, tex=True, pos=pos, lods_loss=not self.only_last)
         return self._fused_cache
 
     def _fused_field_hash(self, grid, dec):
@@ -193,7 +201,9 @@ class SDFTrainStep:
     def _fused_still_valid(self, c):
         nef = self.nef
         grid, dec = c["grid"], c["dec"]
-        if not self.only_last or getattr(nef, "grid", None) is not grid or getattr(nef, "decoder", None) is not dec \
+        all_lods = bool(c.get("lods_loss"))
+        if self.only_last == all_lods or (all_lods and not getattr(self, "fused_lods", False)) \
+                or getattr(nef, "grid", None) is not grid or getattr(nef, "decoder", None) is not dec \
                 or grid.num_lods != c["lods"]:
             return False
         if c.get("triplane"):
@@ -234,6 +244,19 @@ class SDFTrainStep:
             grid._sync_device(coords.device)
             tr = grid.trinkets if grid.trinkets.dtype == torch.int32 else grid.trinkets.int()
             w1, b1, w2, b2 = dec.layers[0].weight, dec.layers[0].bias, dec.lout.weight, dec.lout.bias
+            if fused.get("lods_loss"):
+                # every LOD weighs 1 in the distance term; the reference adds the RUNNING colour sum inside its LOD loop
+                # (sdf_trainer.py:92-101; the modular branch below), so LOD k's colour error counts L - k times
+                tex = bool(fused.get("tex"))
+                colour = rgb[..., :3].reshape(-1, 3).to(torch.float32).contiguous() if tex else None
+                out = C.sdf_lods_train_step(coords, gts, colour, blas.octree, blas.prefix, blas.points, tr,
+                                            [f.detach() for f in grid.features[:L]], grid.active_lods[:L], grid.half_features,
+                                            fused["pos"] if tex else 1, [1.0] * L, [float(L - k) for k in range(L)] if tex else None,
+                                            w1.detach(), b1.detach(), w2.detach(), b2.detach(),
+                                            [f.grad for f in grid.features[:L]], w1.grad, b1.grad, w2.grad, b2.grad)
+                if tex:
+                    self.last_l2, self.last_rgb = out[L], out[2 * L]
+                return out[0]
             if fused.get("tex"):
                 colour = rgb[..., :3].reshape(-1, 3).to(torch.float32).contiguous()
                 out = C.sdf_tex_train_step(coords, gts, colour, blas.octree, blas.prefix, blas.points, tr,

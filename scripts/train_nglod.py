@@ -3,7 +3,7 @@ OctreeAS.from_mesh, OctreeGrid, NeuralSDF, a mesh SDF dataset, SDFTrainer with i
 snapshot (render.png) and the three axis-aligned distance cross-sections (slice_x.png, slice_y.png, slice_z.png).
 
     python scripts/train_nglod.py OBJ [--epochs N] [--dataset octree|mesh] [--grid octree|hash|triplanar] [--fused-step]
-                                  [--fused-kernel] [--out-dir DIR]
+                                  [--fused-kernel] [--all-lods] [--out-dir DIR]
     python scripts/train_nglod.py --write-test-mesh DIR ...
 
 --write-test-mesh DIR first writes the procedural torus of scripts/train_sdf_tex.py into DIR and fits that.
@@ -20,6 +20,11 @@ run through the kernels of csrc/triplane_sdf_eval.hip; the JSON record's fused_t
 --fused-kernel (with --grid triplanar only) trains this field through wisp_triplane_sdf_train_step (csrc/triplane_sdf_train.hip:
 SDFTrainStep(..., fused_triplane=True)), replayed as a HIP graph for whole batches; the JSON record's fused_triplane_step says
 whether the field took that branch.  --grid triplanar --fused-step stays refused.
+--all-lods takes the loss over every level of detail (only_last=False, the reference's default): the field then means something at
+every lod_idx, not at the finest alone.  With --fused-step the octree field trains through wisp_sdf_lods_train_step (csrc/spc_grad.hip:
+SDFTrainStep(..., only_last=False, fused_lods=True)), replayed as a HIP graph; the JSON record's fused_lods_step says whether the field
+took it.  There is no all-LOD fused step over a hash or triplanar grid: --all-lods with one of them and a fused option is refused.
+The record's iou_lods_before / iou_lods_after hold the IoU of every LOD, whatever the loss was taken over.
 The last line printed is one JSON record with the IoU before and after training."""
 import argparse
 import json
@@ -65,17 +70,21 @@ def build(obj, device, level=6, dataset="octree", num_samples=100000, samples_pe
     return ds, Pipeline(nef, PackedSDFTracer(num_steps=128, step_size=0.8, min_dis=0.0003))
 
 
-def fit_fused(trainer, ds, cfg, device, fused_triplane=False):
+def fit_fused(trainer, ds, cfg, device, fused_triplane=False, fused_lods=False):
     """SDFTrainer's epochs with SDFTrainStep: shuffled batches of cfg.dataloader.batch_size, resampling after every epoch.  Returns
-    whether the field took its opt-in fused step (the hash one, or with fused_triplane the triplanar one)."""
+    whether the field took its opt-in fused step (the hash one, with fused_triplane the triplanar one, with fused_lods the all-LOD
+    octree one)."""
     from wisp.trainers import SDFTrainStep
     oc, bs = cfg.optimizer, cfg.dataloader.batch_size
     nef = trainer.pipeline.nef
     from wisp.models.grids import HashGrid, OctreeGrid
     step = SDFTrainStep(nef, lr=oc.lr, eps=oc.eps, grid_lr_weight=cfg.grid_lr_weight, betas=oc.betas, optimizer='adam',
-                        only_last=cfg.only_last, fused_hash=type(nef.grid) is HashGrid, fused_triplane=bool(fused_triplane))
+                        only_last=cfg.only_last, fused_hash=type(nef.grid) is HashGrid, fused_triplane=bool(fused_triplane),
+                        fused_lods=bool(fused_lods))
     on_gpu = torch.device(device).type == 'cuda'
-    took_opt_in = bool(on_gpu and (step.fused_hash or fused_triplane) and step._fused_field() is not None)
+    took_opt_in = bool(on_gpu and (step.fused_hash or fused_triplane or fused_lods) and step._fused_field() is not None)
+    if fused_lods:
+        took_opt_in = bool(took_opt_in and step._fused_field().get("lods_loss"))
     if on_gpu and len(ds) >= bs and (type(nef.grid) is OctreeGrid or took_opt_in):
         step.capture(bs)
     nef.train()
@@ -92,6 +101,20 @@ def fit_fused(trainer, ds, cfg, device, fused_triplane=False):
             trainer.init_dataloader()
     nef.eval()
     return took_opt_in
+
+
+def validate_every_lod(trainer):
+    """SDFTrainer.validate over every LOD of the field, whatever the loss is taken over: {metric: [mean IoU per LOD]} - the last
+    entry is the finest LOD's, the figure validate() gives with only_last"""
+    saved = getattr(trainer, "loss_lods", None)
+    trainer.loss_lods = list(range(trainer.pipeline.nef.grid.num_lods))
+    try:
+        return trainer.validate()
+    finally:
+        if saved is None:
+            del trainer.loss_lods
+        else:
+            trainer.loss_lods = saved
 
 
 def main(argv=None):
@@ -113,6 +136,8 @@ def main(argv=None):
     ap.add_argument("--fused-step", action="store_true")
     ap.add_argument("--fused-kernel", action="store_true",
                     help="--grid triplanar only: train through the kernel-fused step (wisp_triplane_sdf_train_step)")
+    ap.add_argument("--all-lods", action="store_true",
+                    help="loss over every level of detail (only_last=False); with --fused-step: the fused all-LOD octree step")
     ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("W", "H"))
     ap.add_argument("--shading-mode", choices=("rb", "normal", "matcap"), default="normal")
     ap.add_argument("--matcap-path", default=None)
@@ -126,6 +151,9 @@ def main(argv=None):
         args.dataset = "mesh"
     elif args.fused_kernel:
         ap.error("--fused-kernel is the triplanar field's fused step: use it with --grid triplanar (--grid hash: --fused-step)")
+    if args.all_lods and args.grid != "octree" and (args.fused_step or args.fused_kernel):
+        ap.error(f"--all-lods has no fused step over a {args.grid} grid (the all-LOD step is the octree fields'): "
+                 "drop --all-lods, or drop --fused-step / --fused-kernel to train through the modular launches")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     from wisp.ops.image import save_u8
     from wisp.trainers import ConfigAdam, ConfigDataloader, ConfigSDFTrainer, SDFTrainer
@@ -142,17 +170,19 @@ def main(argv=None):
                          num_lods=args.num_lods, num_samples_on_mesh=args.mesh_samples, grid_type=args.grid,
                          codebook_bitwidth=args.codebook_bitwidth)
     cfg = ConfigSDFTrainer(optimizer=ConfigAdam(lr=1e-3, eps=1e-15), dataloader=ConfigDataloader(batch_size=args.batch_size),
-                           max_epochs=args.epochs, resample=True, only_last=True, exp_name='nglod', profile_nvtx=False,
+                           max_epochs=args.epochs, resample=True, only_last=not args.all_lods, exp_name='nglod', profile_nvtx=False,
                            valid_every=-1)
     trainer = SDFTrainer(cfg, pipeline, ds, device=args.device)
     from wisp.ops.sdf import fused_sdf_field
     fld = fused_sdf_field(pipeline.nef) if torch.device(args.device).type == 'cuda' else None
     fused_triplane_eval = bool(args.grid == "triplanar" and fld is not None and fld.get("kind") == "triplane")
-    before = trainer.validate()
+    before = validate_every_lod(trainer)
     metric = next(iter(before))
     t0 = time.time()
-    fused_hash_step = fused_triplane_step = False
-    if args.fused_kernel:
+    fused_hash_step = fused_triplane_step = fused_lods_step = False
+    if args.fused_step and args.all_lods:
+        fused_lods_step = fit_fused(trainer, ds, cfg, args.device, fused_lods=True)
+    elif args.fused_kernel:
         fused_triplane_step = fit_fused(trainer, ds, cfg, args.device, fused_triplane=True)
     elif args.fused_step:
         fused_hash_step = fit_fused(trainer, ds, cfg, args.device)
@@ -162,7 +192,7 @@ def main(argv=None):
         torch.cuda.synchronize()
     seconds = time.time() - t0
     pipeline.eval()
-    after = trainer.validate()
+    after = validate_every_lod(trainer)
     os.makedirs(args.out_dir, exist_ok=True)
     renderer = OfflineRenderer(render_res=tuple(args.size), shading_mode=args.shading_mode,
                                matcap_path=args.matcap_path or './data/matcap/Pearl.png', device=args.device)
@@ -177,7 +207,8 @@ def main(argv=None):
         save_u8(files[f"slice_{name}"], (np.clip(vis, 0, 1) * 255).round().astype(np.uint8).transpose(1, 0, 2))
     rec = dict(obj=os.path.abspath(obj), dataset=args.dataset, grid=args.grid, samples=len(ds), epochs=args.epochs, fused_step=bool(args.fused_step),
                fused_hash_step=fused_hash_step, fused_triplane_eval=fused_triplane_eval, fused_triplane_step=fused_triplane_step,
-               metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
+               all_lods=bool(args.all_lods), fused_lods_step=fused_lods_step, iou_lods_before=list(before[metric]),
+               iou_lods_after=list(after[metric]), metric=metric, iou_before=before[metric][-1], iou_after=after[metric][-1], hits=int(shot.hit.sum()),
                seconds=round(seconds, 3), **{k: os.path.abspath(v) for k, v in files.items()})
     print(json.dumps(rec))
     return rec
