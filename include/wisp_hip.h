@@ -45,7 +45,7 @@ const char* wisp_last_error(void);
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
  * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim, wisp_triplane_sdf_query,
  * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused, wisp_triplane_sdf_train_step,
- * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean, wisp_sdf_lods_train_step - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean, wisp_sdf_lods_train_step, wisp_nerf_octree_query - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -867,6 +867,30 @@ int wisp_nerf_query(const float* coords, const float* dirs, const int64_t* ridx,
                     int dtype_table, int feature_dim, int coord_dim, const int64_t* first_idx, const int32_t* resolutions,
                     int num_lods, int codebook_bitwidth, int zero_from_col, const float* params, int dtype_params, int in_dim,
                     int hidden, float* rgb, float* density, wisp_stream_t stream);
+
+/* The inference query of an octree-backed radiance field (NeuralRadianceField.rgba, wisp/models/nefs/nerf.py:219-264, over
+ * OctreeGrid.interpolate, wisp/models/grids/octree_grid.py:165-219) as ONE launch: for each of `n` sample positions the walk of the
+ * octree from the root to levels[num_lods - 1], the trilinear blend of the eight corner rows on every listed level, their 'sum' or
+ * 'cat' row and the exact-fp32 decoder, written as rgb [n,3] and density [n].  Bit for bit what wisp_spc_query_chain,
+ * wisp_spc_trilinear_multi_fwd and wisp_nerf_mlp_fwd (WISP_F32 compute) give for the same inputs; neither the chain nor a feature
+ * tensor exists.  A CodebookOctreeGrid in eval mode is queried through the rows wisp_codebook_decode_rows(training = 0) writes
+ * (f32 tables, half_round = 0).
+ *  coords, dirs, ridx, num_rays, params, rgb, density: as wisp_nerf_query
+ *  octree u8, exsum i32, points i16 [P,3], trinkets i32 [P,8] (16-byte aligned): the point hierarchy and its dual, as
+ *           wisp_sdf_query takes them; max_level: the octree's depth (<= 15)
+ *  feats    HOST array of num_lods DEVICE tables [rows_l, feature_dim] of dtype_feats (f32 / f16 / bf16)
+ *  levels   i32 [num_lods] HOST: the octree level of every table, ascending, the last at most max_level
+ *  half_round: features and every level's result are rounded through fp16 (OctreeGrid.half_features)
+ *  sum      1: the level sum (in_dim = feature_dim); 0: the 'cat' row (in_dim = num_lods * feature_dim)
+ * A position outside [-1,1]^3, or in an unoccupied cell, gets zero features from there on and the decoder still runs.
+ * This build: feature_dim 1..16, num_lods 1..16, in_dim <= 32, hidden 64, 4 view frequencies, dtype_params = WISP_F32; anything
+ * else returns WISP_ERR_UNSUPPORTED before any launch.  n == 0 returns WISP_OK. */
+int wisp_nerf_octree_query(const float* coords, const float* dirs, const int64_t* ridx, int64_t num_rays, int64_t n,
+                           const uint8_t* octree, const int32_t* exsum, const int16_t* points, const int32_t* trinkets,
+                           int max_level, const void* const* feats, int dtype_feats, const int32_t* levels, int num_lods,
+                           int feature_dim, int half_round, int sum,
+                           const float* params, int dtype_params, int in_dim, int hidden,
+                           float* rgb, float* density, wisp_stream_t stream);
 
 /* The same decoder with the view direction given per RAY.  The reference gathers a direction per sample
  * (wisp/tracers/packed_rf_tracer.py:70-76 `rays.dirs.index_select(0, ridx)`) and positional_embedder.py:61-65 encodes each

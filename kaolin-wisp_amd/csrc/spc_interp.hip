@@ -38,6 +38,12 @@ spc_trilinear_coeffs_kernel(const float* __restrict__ coords, const int16_t* __r
     for (int j = 0; j < 8; ++j) out[i * 8 + j] = w[j];
 }
 
+// The blend of the three forward kernels below is spelled as the fmaf chain over the corners in corner order.  Written as
+// `acc += fv * w[j]` the compiler fused some of the eight products and not others, differently per instantiation (the f32 kernels
+// rounded the products of corners 3 and 4 on their own, the f16 ones all eight), so the same lookup gave results one fp32 ulp
+// apart depending on the table's dtype, on the sample count (which picks the kernel) and on whether one level or several were
+// asked for - and apart from codebook_trilinear_fwd_kernel, sdf_eval_dev.h and octree_nerf_eval_dev.h, which all run the chain.
+// For the same reason a level's finished result goes through wisp_round_through_f16 (wisp_common.h) behind half_round.
 template <typename T, typename I>
 __global__ void __launch_bounds__(256)
 spc_trilinear_fwd_kernel(const float* __restrict__ coords, const I* __restrict__ pidx, const int16_t* __restrict__ points,
@@ -64,9 +70,9 @@ spc_trilinear_fwd_kernel(const float* __restrict__ coords, const I* __restrict__
             for (int j = 0; j < 8; ++j) {
                 float fv = Cvt<T>::to_f(feats[(int64_t)tr[j] * channels + ch]);
                 if (half_round) fv = __half2float(__float2half_rn(fv));
-                acc += fv * w[j];
+                acc = __builtin_fmaf(fv, w[j], acc);
             }
-            out[i * channels + ch] = half_round ? __half2float(__float2half_rn(acc)) : acc;
+            out[i * channels + ch] = half_round ? wisp_round_through_f16(acc) : acc;
         }
     }
 }
@@ -147,9 +153,9 @@ spc_trilinear_multi_fwd_kernel(const float* __restrict__ coords, const int64_t* 
                     for (int j = 0; j < 8; ++j) {
                         float fv = Cvt<T>::to_f(feats[(int64_t)tr[j] * channels + ch]);
                         if (half_round) fv = __half2float(__float2half_rn(fv));
-                        acc += fv * w[j];
+                        acc = __builtin_fmaf(fv, w[j], acc);
                     }
-                    if (half_round) acc = __half2float(__float2half_rn(acc));
+                    if (half_round) acc = wisp_round_through_f16(acc);
                 }
                 if (sum) total += acc; else out[i * out_row + l * channels + ch] = acc;
             }
@@ -202,12 +208,12 @@ spc_trilinear_multi_fwd_small_kernel(const float* __restrict__ coords, const int
                 for (int ch = 0; ch < C; ++ch) {
                     float fv = Cvt<T>::to_f(row[ch]);
                     if (half_round) fv = __half2float(__float2half_rn(fv));
-                    acc[ch] += fv * w[j];
+                    acc[ch] = __builtin_fmaf(fv, w[j], acc[ch]);
                 }
             }
             if (half_round)
 #pragma unroll
-                for (int ch = 0; ch < C; ++ch) acc[ch] = __half2float(__float2half_rn(acc[ch]));
+                for (int ch = 0; ch < C; ++ch) acc[ch] = wisp_round_through_f16(acc[ch]);
         }
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {

@@ -62,6 +62,15 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 static inline int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
 // ---- storage-type conversion (tables / activations may be f32, f16 or bf16) ------------------------
+// A finished fp32 value rounded through fp16, in two steps whatever produced it.  Where the conversion directly follows an fma the
+// compiler may fold both into v_fma_mixlo_f16, which rounds the exact sum once: it did so in some instantiations of the
+// trilinear lookups and not in others, and on the rare values whose fp32 rounding lands on an fp16 tie (about one in 2^13) the
+// two differ by an fp16 ulp.  The empty asm pins the fp32 value in a register, so the conversion is always the separate one.
+static __device__ __forceinline__ float wisp_round_through_f16(float v) {
+    asm volatile("" : "+v"(v));
+    return __half2float(__float2half_rn(v));
+}
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
     static __device__ __forceinline__ float to_f(float v) { return v; }

@@ -145,6 +145,8 @@ SIGNATURES = {
                                     c_i32, c_i32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "wisp_nerf_query": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32,
                         c_i32, c_vp, c_vp, c_vp],
+    "wisp_nerf_octree_query": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
+                               c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp],
     "wisp_nerf_mlp_dir_code": [c_vp, c_i64, c_i32, c_vp, c_vp],
     "wisp_nerf_mlp_operand_image_bytes": [c_i32],
     "wisp_nerf_mlp_build_operand_image": [c_vp, c_i32, c_i32, c_vp, c_vp],
@@ -2316,6 +2318,65 @@ def nerf_query(coords, dirs, ridx, codebook, first_idx, resolutions, codebook_bi
                                    coords.shape[1], _p(first_idx), res_ptr, L, codebook_bitwidth, zero_from_col, _p(params),
                                    _DTYPE_CODE.get(params.dtype, -1), in_dim, hidden,
                                    _p(rgb[pad_rows:] if rgb is not None else None), _p(density[pad_rows:]), _stream()), "nerf_query")
+    return rgb, density
+
+
+def nerf_octree_query(coords, dirs, ridx, octree, exsum, points, trinkets, max_level, feats_list, levels, half_round, sum_lods,
+                      params, in_dim, hidden, want_rgb=True, pad_rows=0):
+    """(rgb f32 [n, 3] or None, density f32 [n]) - octree walk, multi-level trilinear lookup and exact-fp32 decoder of an
+    octree-backed radiance field in one launch (wisp_nerf_octree_query), bit for bit spc_query_chain + spc_trilinear_multi_forward
+    followed by nerf_mlp_forward with fp32 compute.  feats_list: one [rows_l, F] table per entry of `levels` (ascending octree
+    levels), all of one dtype (f32 / f16 / bf16).  dirs / ridx / want_rgb / pad_rows: as nerf_query."""
+    coords = _need(coords, torch.float32, "coords")
+    octree = _need(octree, torch.uint8, "octree")
+    exsum = _need(exsum, torch.int32, "exsum")
+    points = _need(points, torch.int16, "points")
+    trinkets = _need(trinkets, torch.int32, "trinkets")
+    params = _need(params, None, "params")
+    feats_list = [_need(f, None, "feats") for f in feats_list]
+    n = coords.shape[0]
+    if coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"coords must be [n, 3], got {tuple(coords.shape)}")
+    R = 0
+    if ridx is not None:
+        ridx = _need(ridx, torch.int64, "ridx")
+        if dirs is None or ridx.shape != (n,):
+            raise ValueError("ridx must be [n] and needs the rays' directions")
+    if dirs is not None:
+        dirs = _need(dirs, torch.float32, "dirs")
+        R = dirs.shape[0]
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or (ridx is None and R != n) or (ridx is not None and n > 0 and R < 1):
+            raise ValueError(f"dirs must be [n, 3], or [R >= 1, 3] with ridx; got {tuple(dirs.shape)} for {n} samples")
+    elif want_rgb:
+        raise ValueError("the colour needs view directions")
+    L = len(feats_list)
+    if L < 1 or len(levels) != L:
+        raise ValueError("one octree level per feature table")
+    F = feats_list[0].shape[1]
+    if any(f.dim() != 2 or f.shape[1] != F or f.dtype != feats_list[0].dtype for f in feats_list):
+        raise ValueError("the feature tables must be [rows, F] of one width and dtype")
+    if points.dim() != 2 or points.shape[1] != 3 or tuple(trinkets.shape) != (points.shape[0], 8) \
+            or exsum.numel() < octree.numel() + 1:
+        raise ValueError("points [P,3], trinkets [P,8] and exsum [len(octree)+1] of one octree are needed")
+    want = int(lib.wisp_nerf_mlp_param_count(in_dim, hidden, 4))
+    if params.numel() != want:
+        raise ValueError(f"packed decoder parameters: expected {want} floats for in_dim={in_dim}, got {params.numel()}")
+    farr, fptr = _ptr_array(feats_list)
+    larr, lptr = _host_i32(levels)
+    dev = coords.device
+    rows = n + 2 * pad_rows
+    rgb = torch.empty(rows, 3, dtype=torch.float32, device=dev) if want_rgb else None
+    density = torch.empty(rows, dtype=torch.float32, device=dev)
+    if pad_rows:
+        density.fill_(float("nan"))
+        if rgb is not None:
+            rgb.fill_(float("nan"))
+    with _timed("nerf_octree_query", n):
+        _check(lib.wisp_nerf_octree_query(_p(coords), _p(dirs), _p(ridx), R, n, _p(octree), _p(exsum), _p(points), _p(trinkets),
+                                          int(max_level), fptr, _DTYPE_CODE.get(feats_list[0].dtype, -1), lptr, L, F,
+                                          int(bool(half_round)), int(bool(sum_lods)), _p(params), _DTYPE_CODE.get(params.dtype, -1),
+                                          in_dim, hidden, _p(rgb[pad_rows:] if rgb is not None else None), _p(density[pad_rows:]),
+                                          _stream()), "nerf_octree_query")
     return rgb, density
 
 

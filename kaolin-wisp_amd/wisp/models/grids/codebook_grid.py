@@ -45,6 +45,21 @@ class CodebookOctreeGrid(OctreeGrid):
         for i, f in enumerate(self.features):
             self.features[i] = nn.Parameter(f.max(dim=-1)[1].float())
 
+    def decoded_tables(self):
+        """The eval-mode feature table of every level, `dictionary[argmax(logits_row)]` (first index on ties) as fp32 [rows, F]:
+        what the one-launch field query reads (wisp.ops.nerf_mlp.fused_nerf_octree_query).  Kept in the plain attribute
+        `_decoded_cache` - neither a parameter nor a buffer, so not in state_dict - and rebuilt whenever the `_version` or
+        `data_ptr` of any level's logits or dictionary differs from what was recorded (an optimizer step, load_state_dict, a
+        move to another device), or a trainer's raw-pointer optimizer has run since."""
+        import wisp._C as C
+        key = (grid_ops.raw_write_epoch(),) + tuple((t._version, t.data_ptr()) for pair in zip(self.features, self.dictionary)
+                                                     for t in pair)
+        cache = self.__dict__.get('_decoded_cache')
+        if cache is None or cache[0] != key:
+            tables = [C.codebook_decode_rows(f.detach(), d.detach(), False) for f, d in zip(self.features, self.dictionary)]
+            cache = self.__dict__['_decoded_cache'] = (key, tables)
+        return cache[1]
+
     def _index_features(self, feats, idx, lod_idx):
         """Dictionary vectors for corner indices: straight-through one-hot of softmax(logits) in training,
         plain argmax lookup in eval (codebook_grid.py:103-136)."""

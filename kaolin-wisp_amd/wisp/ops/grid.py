@@ -106,6 +106,19 @@ def mark_shadow_current(codebook):
         aux.shadow_version = codebook._version
 
 
+# Bumped whenever a trainer's raw-pointer optimizer kernel rewrote parameters without touching their autograd version counters
+# (FlatParams.mark_shadow_current): what a cache derived from parameter VALUES keys on next to `_version` and `data_ptr`.
+_RAW_WRITE_EPOCH = [0]
+
+
+def note_raw_parameter_write():
+    _RAW_WRITE_EPOCH[0] += 1
+
+
+def raw_write_epoch():
+    return _RAW_WRITE_EPOCH[0]
+
+
 def current_shadow(codebook, dtype):
     """The registered copy of `codebook` in `dtype` if it is known to mirror the master weights, else None."""
     aux = _TABLE_AUX.get(codebook)

@@ -201,6 +201,91 @@ def fused_nerf_query(nef, coords, ray_d=None, ray_dirs=None, ridx=None, lod_idx=
     return rgb, density.reshape(-1, 1)
 
 
+def nerf_octree_query_supported(nef, lod_idx=None):
+    """The fused inference query of the octree family (csrc/nerf_octree_query.hip) covers this field: a CUDA OctreeGrid whose
+    multi-level lookup is the one-launch one (`_fusable()`), or a CUDA CodebookOctreeGrid in eval mode with 2-D fp32 logits (not
+    baked), an fp32 dictionary of at most 256 entries and at most 16 features; 'linear' interpolation; 'sum' at any valid
+    lod_idx, or 'cat' at the last one; and the decoder conditions of nerf_query_supported.  The switch
+    WISP_NERF_OCTREE_QUERY_FUSED must be set to something other than 0: its default is off, because on the nerf_octree.yaml field
+    a whole view at render_batch 10 000 did not beat the modular ops outside the spread of the repetitions
+    (profiles/bench_nerf_octree_eval.json)."""
+    import os
+    from wisp.models.grids import CodebookOctreeGrid, OctreeGrid
+    if os.environ.get("WISP_NERF_OCTREE_QUERY_FUSED", "0") == "0" or not getattr(nef, 'fused_decoder', False) \
+            or torch.is_autocast_enabled():
+        return False
+    grid = nef.grid
+    if not isinstance(grid, OctreeGrid) or grid.interpolation_type != 'linear' or grid.multiscale_type not in ('cat', 'sum') \
+            or not 1 <= grid.num_lods <= 16 or len(grid.active_lods) != grid.num_lods or not 1 <= grid.feature_dim <= 16:
+        return False
+    last = grid.num_lods - 1
+    if lod_idx is None:
+        lod_idx = last
+    if not 0 <= lod_idx <= last or (grid.multiscale_type == 'cat' and lod_idx != last):
+        return False
+    if isinstance(grid, CodebookOctreeGrid):
+        if grid.training or type(grid)._interpolate is not CodebookOctreeGrid._interpolate or not getattr(grid, 'fused', False):
+            return False
+        for logits, dictionary in zip(grid.features, grid.dictionary):
+            if not logits.is_cuda or not dictionary.is_cuda or logits.ndim != 2 or logits.dtype != torch.float32 \
+                    or dictionary.dtype != torch.float32 or logits.shape[1] != dictionary.shape[0] \
+                    or not dictionary.shape[1] <= dictionary.shape[0] <= 256 or dictionary.shape[1] != grid.feature_dim:
+                return False
+    else:
+        if not grid._fusable() or any(not f.is_cuda or f.dtype != grid.features[0].dtype or f.ndim != 2 for f in grid.features) \
+                or grid.features[0].dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            return False
+    if nef.hidden_dim != SUPPORTED["hidden"] or _compute_bf16(nef) or nef.effective_feature_dim() > SUPPORTED["max_in_dim"]:
+        return False
+    from types import SimpleNamespace
+    if not supports(nef, SimpleNamespace(is_cuda=True, shape=(0, nef.effective_feature_dim()), dtype=torch.float32)):
+        return False                                       # (what the lookup would hand the decoder: fp32 rows on the grid's device)
+    return not any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in _decoder_tensors(nef))
+
+
+def fused_nerf_octree_query(nef, coords, ray_d=None, ray_dirs=None, ridx=None, lod_idx=None, want_rgb=True, pad_rows=0):
+    """(rgb [n,3] fp32 or None, density [n,1] fp32) of NeuralRadianceField.rgba for a field nerf_octree_query_supported() accepts,
+    in one launch and without a chain or a feature tensor; the same bits as grid.interpolate + fused_nerf_decoder (for a codebook
+    grid's 'sum' over three or more levels: up to the order in which torch adds the levels).  A codebook grid is read through its
+    decoded rows (CodebookOctreeGrid.decoded_tables).  View directions as fused_nerf_query takes them.  Inference only: inputs
+    that require a gradient are refused."""
+    from wisp.models.grids import CodebookOctreeGrid
+    grid = nef.grid
+    codebook = isinstance(grid, CodebookOctreeGrid)
+    tensors = [coords, ray_d, ray_dirs] + list(grid.features) + (list(grid.dictionary) if codebook else []) + _decoder_tensors(nef)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError("fused_nerf_octree_query has no backward: call it under torch.no_grad(), or take the modular path")
+    if (ray_d is None) == (ray_dirs is None) and want_rgb:
+        raise ValueError("give the view direction either per sample (ray_d) or per ray (ray_dirs + ridx)")
+    if (ray_dirs is None) != (ridx is None):
+        raise ValueError("ray_dirs and ridx go together")
+    C = _hip()
+    C._need(coords, torch.float32, "coords")               # a field or positions on the CPU: no fallback
+    C._need(grid.features[0], None, "features")
+    if lod_idx is None:
+        lod_idx = len(grid.active_lods) - 1
+    sum_lods = grid.multiscale_type == 'sum'
+    if not 0 <= lod_idx < len(grid.active_lods) or (not sum_lods and lod_idx != len(grid.active_lods) - 1):
+        raise ValueError(f"lod_idx {lod_idx}: 'sum' takes any level of the grid, 'cat' the last one")
+    params = _decoder_tensors(nef)
+    H, I = nef.hidden_dim, nef.effective_feature_dim()
+    shapes = ((H, I), (H,), (16, H), (16,), (H, 42), (H,), (H, H), (H,), (3, H), (3,))
+    flat = _flat_view([p.detach() if p is not None else None for p in params])
+    packed = flat if flat is not None else _pack(params, shapes)
+    num = lod_idx + 1
+    grid._sync_device(coords.device)
+    if codebook:
+        tables, half_round = grid.decoded_tables()[:num], False
+    else:
+        tables, half_round = [grid.features[i].detach() for i in range(num)], bool(grid.half_features)
+    trinkets = grid.trinkets if grid.trinkets.dtype == torch.int32 else grid.trinkets.int()
+    rgb, density = C.nerf_octree_query(coords.detach(), (ray_d if ray_d is not None else ray_dirs), ridx, grid.blas.octree,
+                                       grid.blas.prefix, grid.blas.points, trinkets.contiguous(), grid.blas.max_level, tables,
+                                       [int(l) for l in grid.active_lods[:num]], half_round, sum_lods, packed, I, H,
+                                       want_rgb=want_rgb, pad_rows=pad_rows)
+    return rgb, density.reshape(-1, 1)
+
+
 def fused_nerf_decoder(nef, feats, ray_d):
     """(rgb [S,3] fp32, density [S,1] fp32) for the decoder shapes of the reference's app/nerf configs (see SUPPORTED)."""
     compute_bf16 = _compute_bf16(nef)

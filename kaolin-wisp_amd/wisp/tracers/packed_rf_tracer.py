@@ -54,13 +54,18 @@ class PackedRFTracer(BaseTracer):
         return {"rgb", "density"}
 
     def _fused_query(self, nef, lod_idx, extra_channels):
-        """True when this call takes the one-launch field query: the plain attribute `fused_query` is set (absent = off; not a
+        """The one-launch field query this call takes, or None: the plain attribute `fused_query` is set (absent = off; not a
         constructor argument, the schema is the reference's), gradients are disabled, no extra channel is asked for and the field
-        is one wisp.ops.nerf_mlp.nerf_query_supported accepts."""
+        is one wisp.ops.nerf_mlp.nerf_query_supported accepts (the hash route) or, failing that, one
+        nerf_octree_query_supported accepts (the octree route: OctreeGrid and CodebookOctreeGrid fields)."""
         if not getattr(self, 'fused_query', False) or torch.is_grad_enabled() or extra_channels:
-            return False
-        from wisp.ops.nerf_mlp import nerf_query_supported
-        return nerf_query_supported(nef, lod_idx)
+            return None
+        import wisp.ops.nerf_mlp as ops
+        if ops.nerf_query_supported(nef, lod_idx):
+            return ops.fused_nerf_query
+        if ops.nerf_octree_query_supported(nef, lod_idx):
+            return ops.fused_nerf_octree_query
+        return None
 
     def trace(self, nef, rays, channels, extra_channels,
               lod_idx=None, raymarch_type='voxel', num_steps=64, step_size=1.0, bg_color='white', jitter=None):
@@ -76,12 +81,13 @@ class PackedRFTracer(BaseTracer):
         num_samples = samples.shape[0]
         self.prev_num_samples = num_samples
 
-        if self._fused_query(nef, lod_idx, extra_channels):
-            # inference on the shipped NeRF shape: lookup + decoder as ONE launch that reads every sample's direction through its
-            # ray index (csrc/nerf_query.hip) - no per-sample direction tensor, no feature tensor; same bits as the calls below
-            from wisp.ops.nerf_mlp import fused_nerf_query
+        fused_query = self._fused_query(nef, lod_idx, extra_channels)
+        if fused_query is not None:
+            # inference on a shipped NeRF shape: lookup + decoder as ONE launch that reads every sample's direction through its
+            # ray index (csrc/nerf_query.hip for hash grids, csrc/nerf_octree_query.hip for octree and codebook grids) - no
+            # per-sample direction tensor, no feature tensor; same bits as the calls below
             hit_ray_d = None
-            color, density = fused_nerf_query(nef, samples, ray_dirs=rays.dirs, ridx=ridx, lod_idx=lod_idx)
+            color, density = fused_query(nef, samples, ray_dirs=rays.dirs, ridx=ridx, lod_idx=lod_idx)
         else:
             hit_ray_d = rays.dirs.index_select(0, ridx)
             color = None

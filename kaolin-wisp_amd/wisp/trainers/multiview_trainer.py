@@ -21,7 +21,7 @@ import torch
 import torch.distributed as dist
 
 from wisp.core import Rays
-from wisp.ops.grid import current_shadow, mark_shadow_current, register_table_aux
+from wisp.ops.grid import current_shadow, mark_shadow_current, note_raw_parameter_write, register_table_aux
 from wisp.trainers.base_trainer import BaseTrainer, ConfigBaseTrainer
 
 
@@ -90,6 +90,7 @@ class FlatParams:
                 mark_shadow_current(p)
 
     def mark_shadow_current(self):
+        note_raw_parameter_write()       # (caches of decoded codebook rows: the kernels do not bump `_version`)
         for p, _ in self._grid_params:
             mark_shadow_current(p)
 

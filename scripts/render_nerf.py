@@ -2,7 +2,7 @@
 per view, one JSON line with the timing.
 
     python scripts/render_nerf.py --checkpoint PATH [--views 8] [--res 800 800] [--render-batch 10000] --out DIR [--no-fused]
-    python scripts/render_nerf.py --write-synlego DIR --steps K [...] --out DIR
+    python scripts/render_nerf.py --write-synlego DIR --steps K [--grid hash|octree|codebook] [...] --out DIR
 
 --checkpoint PATH is a file written by wisp.trainers.validation.save_pipeline: a 'full' checkpoint is the pipeline itself, a
 state_dict checkpoint is loaded into the nerf_hash.yaml pipeline of scripts/train_nerf_synthetic.py.  With --write-synlego DIR a
@@ -11,7 +11,12 @@ neither a dataset nor a checkpoint exists.
 
 The views are traced through wisp.trainers.validation.render with the tracer's `fused_query` on - lookup + decoder of every chunk
 in one launch (csrc/nerf_query.hip), the same bits as the modular ops - unless --no-fused is given or the field is not one the
-kernel covers (the JSON line reports which)."""
+kernel covers (the JSON line reports which).
+
+--grid octree / codebook (with --write-synlego) builds the field of nerf_octree.yaml / nerf_codebook.yaml instead - OctreeGrid or
+4-bit CodebookOctreeGrid, 5 features, 4 LODs, 'sum', bias-free decoders, 'voxel' march with 16 steps - on an octree built from the
+scene's surface point cloud; its views go through the one-launch query of csrc/nerf_octree_query.hip (`fused_octree_query` in the
+JSON line)."""
 import argparse
 import json
 import logging
@@ -42,8 +47,28 @@ def orbit_cameras(views, width, height, elevation_cos=0.5):
     return cams
 
 
-def fit_synlego(root, steps, dev, views=8, res=64, num_steps=512, num_samples=1024):
-    """write a small SynLego scene to `root` and fit the nerf_hash.yaml pipeline to it for `steps` iterations"""
+def build_octree_pipeline(dev, kind, level, cloud_rays, bg_color=(0.0, 0.0, 0.0)):
+    """nerf_octree.yaml (kind 'octree') / nerf_codebook.yaml (kind 'codebook'): the octree of the scene's surface point cloud (as
+    bench_configs.vqad_scene builds it), F = 5, 4 LODs, 'sum', bias-free hidden-64 decoders, 'voxel' march with 16 steps."""
+    import synlego
+    from wisp.accelstructs import OctreeAS
+    from wisp.models import Pipeline
+    from wisp.models.grids import CodebookOctreeGrid, OctreeGrid
+    from wisp.models.nefs import NeuralRadianceField
+    from wisp.tracers import PackedRFTracer
+    blas = OctreeAS.from_pointcloud(synlego.v8_pointcloud(cloud_rays, res=400, device=dev), level)
+    shape = dict(feature_dim=5, num_lods=4, interpolation_type='linear', multiscale_type='sum', feature_std=0.01, feature_bias=0.0)
+    grid = CodebookOctreeGrid(blas, codebook_bitwidth=4, **shape) if kind == "codebook" else OctreeGrid(blas, **shape)
+    nef = NeuralRadianceField(grid, pos_embedder='none', view_embedder='positional', view_multires=4, activation_type='relu',
+                              layer_type='linear', hidden_dim=64, num_layers=1, bias=False, prune_density_decay=None,
+                              prune_min_density=None).to(dev)
+    return Pipeline(nef, PackedRFTracer(raymarch_type='voxel', num_steps=16, step_size=1.0, bg_color=tuple(bg_color)))
+
+
+def fit_synlego(root, steps, dev, views=8, res=64, num_steps=512, num_samples=1024, grid="hash", octree_level=8,
+                cloud_rays=1 << 21):
+    """write a small SynLego scene to `root` and fit the nerf_hash.yaml pipeline (grid 'hash'), or the nerf_octree.yaml /
+    nerf_codebook.yaml one, to it for `steps` iterations"""
     from train_nerf_synthetic import build_pipeline, write_synlego_scene
     from wisp.datasets import SampleRays, load_multiview_dataset
     from wisp.trainers import ConfigAdamW, ConfigMultiviewTrainer, MultiviewTrainer
@@ -51,10 +76,11 @@ def fit_synlego(root, steps, dev, views=8, res=64, num_steps=512, num_samples=10
     train = load_multiview_dataset(root, split='train', transform=SampleRays(num_samples), bg_color=(0.0, 0.0, 0.0), mip=0,
                                    dataset_num_workers=-1)
     torch.manual_seed(0)
-    pipeline = build_pipeline(dev, num_steps, (0.0, 0.0, 0.0))
+    pipeline = (build_pipeline(dev, num_steps, (0.0, 0.0, 0.0)) if grid == "hash" else
+                build_octree_pipeline(dev, grid, octree_level, cloud_rays))
     epochs = max(1, -(-(steps + 1) // len(train)))                      # (the first iteration only sizes the batch)
     cfg = ConfigMultiviewTrainer(optimizer=ConfigAdamW(lr=1e-3, eps=1e-16, weight_decay=1e-6), grid_lr_weight=500.0, enable_amp=True,
-                                 prune_every=100, rgb_loss_type='huber', rgb_loss_denom='rays', max_epochs=epochs, scheduler=True,
+                                 prune_every=100 if grid == "hash" else -1, rgb_loss_type='huber', rgb_loss_denom='rays', max_epochs=epochs, scheduler=True,
                                  valid_every=-1, save_every=-1, profile_nvtx=False)
     trainer = MultiviewTrainer(cfg, pipeline, train, device=dev)
     trainer.is_optimization_running = True
@@ -76,15 +102,21 @@ def main(argv=None):
     ap.add_argument("--render-batch", type=int, default=10000, help="rays per chunk")
     ap.add_argument("--out", metavar="DIR", required=True)
     ap.add_argument("--no-fused", action="store_true", help="leave the tracer's fused_query off (the modular ops)")
+    ap.add_argument("--grid", choices=("hash", "octree", "codebook"), default="hash",
+                    help="--write-synlego: the field to fit - nerf_hash.yaml, nerf_octree.yaml or nerf_codebook.yaml")
+    ap.add_argument("--octree-level", type=int, default=8, help="--grid octree / codebook: depth of the scene's octree")
+    ap.add_argument("--cloud-rays", type=int, default=1 << 21, help="--grid octree / codebook: rays of the surface point cloud")
     args = ap.parse_args(argv)
     if (args.checkpoint is None) == (args.write_synlego is None):
         ap.error("give exactly one of --checkpoint PATH and --write-synlego DIR")
+    if args.grid != "hash" and args.write_synlego is None:
+        ap.error("--grid octree / codebook builds its field with --write-synlego (a 'full' checkpoint carries its own grid)")
     logging.basicConfig(level=logging.WARNING, format="%(message)s")
     assert torch.cuda.is_available(), "render_nerf.py renders on the GPU"
     dev = "cuda:0"
     from wisp.core import RenderBuffer
     from wisp.ops.image import write_png
-    from wisp.ops.nerf_mlp import nerf_query_supported
+    from wisp.ops.nerf_mlp import nerf_octree_query_supported, nerf_query_supported
     from wisp.ops.raygen import generate_centered_pixel_coords, generate_pinhole_rays
     from wisp.trainers.validation import load_pipeline, render
     if args.checkpoint is not None:
@@ -97,7 +129,8 @@ def main(argv=None):
             pipeline = obj
         pipeline = pipeline.to(dev)
     else:
-        pipeline = fit_synlego(args.write_synlego, args.steps, dev, views=args.train_views, res=args.train_res, num_steps=args.num_steps)
+        pipeline = fit_synlego(args.write_synlego, args.steps, dev, views=args.train_views, res=args.train_res, num_steps=args.num_steps,
+                               grid=args.grid, octree_level=args.octree_level, cloud_rays=args.cloud_rays)
     pipeline.eval()
     h, w = args.res
     fused = not args.no_fused
@@ -123,12 +156,14 @@ def main(argv=None):
     grid_ = pipeline.nef.grid
     with torch.no_grad():
         took_fused = bool(fused and nerf_query_supported(pipeline.nef))
+        took_octree = bool(fused and not took_fused and nerf_octree_query_supported(pipeline.nef))
     print(json.dumps(dict(metric="render_nerf", frames=len(times), res=[h, w], render_batch=args.render_batch,
                           ms_per_frame=round(sum(times) / max(len(times), 1), 3),
                           samples_per_frame=int(sum(samples) / max(len(samples), 1)), fused_query=took_fused,
+                          grid=args.grid, fused_octree_query=took_octree,
                           field=dict(grid=type(grid_).__name__, num_lods=int(getattr(grid_, "num_lods", 0)),
                                      feature_dim=int(getattr(grid_, "feature_dim", 0)),
-                                     codebook_bitwidth=int(getattr(grid_, "codebook_bitwidth", 0)),
+                                     codebook_bitwidth=int(getattr(grid_, "codebook_bitwidth", getattr(grid_, "bitwidth", 0))),
                                      multiscale_type=getattr(grid_, "multiscale_type", None),
                                      hidden_dim=int(pipeline.nef.hidden_dim)))))
 
