@@ -45,7 +45,8 @@ const char* wisp_last_error(void);
  * wisp_nerf_mlp_bwd_rays_partials, wisp_nerf_mlp_bwd_rays_img_partials, wisp_nerf_mlp_reduce_partials,
  * wisp_hashgrid_interpolate_bwd_adamw_tail, wisp_spc_first_hit, wisp_ssim, wisp_triplane_sdf_query,
  * wisp_triplane_sdf_fd_gradient, wisp_triplane_sdf_trace_step_fused, wisp_triplane_sdf_train_step,
- * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean, wisp_sdf_lods_train_step, wisp_nerf_octree_query - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
+ * wisp_hashgrid_interpolate_bwd_adamw_flags, wisp_nerf_step_grad_clean, wisp_sdf_lods_train_step, wisp_nerf_octree_query,
+ * wisp_nerf_triplane_query - do not bump it; nor does wisp_nerf_step_hyper.tail_fold, which took the place of a
  * reserved field that callers zeroed). */
 int wisp_abi_version(void);
 
@@ -891,6 +892,26 @@ int wisp_nerf_octree_query(const float* coords, const float* dirs, const int64_t
                            int feature_dim, int half_round, int sum,
                            const float* params, int dtype_params, int in_dim, int hidden,
                            float* rgb, float* density, wisp_stream_t stream);
+
+/* The inference query of a triplanar radiance field (NeuralRadianceField.rgba, wisp/models/nefs/nerf.py:219-264, over
+ * TriplanarGrid.interpolate, wisp/models/grids/triplanar_grid.py:97-146 and :205-233) as ONE launch: for each of `n` sample
+ * positions three bilinear lookups per level (align_corners=True, reflection padding: wisp_reflect_source_index; plane x takes
+ * (y, z), plane y (x, z), plane z (x, y); grid[..., 0] indexes the width), the columns [x | y | z], the levels 'cat'-ed behind one
+ * another or added in level order in fp32 from +0.0f ('sum'), and the exact-fp32 decoder, written as rgb [n,3] and density [n].  No
+ * feature tensor exists.  The feature row is the bits of the triplanar SDF kernels' encoder (tri_sdf_blend: every rounding spelled
+ * out); wisp_triplane_fwd leaves its contraction to the compiler and agrees to rounding.  The decoder is bit for bit
+ * wisp_nerf_mlp_fwd (WISP_F32 compute) on the same rows.
+ *  coords, dirs, ridx, num_rays, params, rgb, density: as wisp_nerf_query
+ *  planes   HOST array of 3 * num_lods DEVICE f32 planes [feature_dim, size_l, size_l]: x, y, z of level 0, then level 1, ...
+ *  sizes    i32 [num_lods] HOST, each >= 1;  feature_dim: per plane
+ *  sum      1: the level sum (in_dim = 3 * feature_dim); 0: the 'cat' row (in_dim = num_lods * 3 * feature_dim)
+ *  feats_out NULL, or f32 [n, in_dim]: the decoder's input rows (for tests)
+ * This build: num_lods 1..16, feature_dim >= 1, in_dim <= 32, hidden 64, 4 view frequencies, dtype_params = WISP_F32; anything
+ * else returns WISP_ERR_UNSUPPORTED before any launch.  n == 0 returns WISP_OK. */
+int wisp_nerf_triplane_query(const float* coords, const float* dirs, const int64_t* ridx, int64_t num_rays, int64_t n,
+                             const float* const* planes, const int32_t* sizes, int num_lods, int feature_dim, int sum,
+                             const float* params, int dtype_params, int in_dim, int hidden,
+                             float* rgb, float* density, float* feats_out, wisp_stream_t stream);
 
 /* The same decoder with the view direction given per RAY.  The reference gathers a direction per sample
  * (wisp/tracers/packed_rf_tracer.py:70-76 `rays.dirs.index_select(0, ridx)`) and positional_embedder.py:61-65 encodes each

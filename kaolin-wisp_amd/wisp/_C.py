@@ -147,6 +147,8 @@ SIGNATURES = {
                         c_i32, c_vp, c_vp, c_vp],
     "wisp_nerf_octree_query": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
                                c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp],
+    "wisp_nerf_triplane_query": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                 c_vp, c_vp],
     "wisp_nerf_mlp_dir_code": [c_vp, c_i64, c_i32, c_vp, c_vp],
     "wisp_nerf_mlp_operand_image_bytes": [c_i32],
     "wisp_nerf_mlp_build_operand_image": [c_vp, c_i32, c_i32, c_vp, c_vp],
@@ -2378,6 +2380,62 @@ def nerf_octree_query(coords, dirs, ridx, octree, exsum, points, trinkets, max_l
                                           in_dim, hidden, _p(rgb[pad_rows:] if rgb is not None else None), _p(density[pad_rows:]),
                                           _stream()), "nerf_octree_query")
     return rgb, density
+
+
+def nerf_triplane_query(coords, dirs, ridx, planes, sizes, feature_dim, sum_lods, params, in_dim, hidden, want_rgb=True, pad_rows=0,
+                        want_feats=False):
+    """(rgb f32 [n, 3] or None, density f32 [n]) - the three bilinear plane lookups of every level and the exact-fp32 decoder of a
+    triplanar radiance field in one launch (wisp_nerf_triplane_query): the feature rows of the triplanar SDF kernels' encoder
+    followed, bit for bit, by nerf_mlp_forward with fp32 compute.  planes: f32 [x0, y0, z0, x1, ...], each [1 or -, feature_dim,
+    sizes[l], sizes[l]].  dirs / ridx / want_rgb / pad_rows: as nerf_query.  want_feats (tests): a third result, the decoder's
+    input rows f32 [n, in_dim], guarded by pad_rows like the others."""
+    coords = _need(coords, torch.float32, "coords")
+    params = _need(params, None, "params")
+    planes = [_need(p, None, "plane") for p in planes]
+    n = coords.shape[0]
+    if coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"coords must be [n, 3], got {tuple(coords.shape)}")
+    R = 0
+    if ridx is not None:
+        ridx = _need(ridx, torch.int64, "ridx")
+        if dirs is None or ridx.shape != (n,):
+            raise ValueError("ridx must be [n] and needs the rays' directions")
+    if dirs is not None:
+        dirs = _need(dirs, torch.float32, "dirs")
+        R = dirs.shape[0]
+        if dirs.dim() != 2 or dirs.shape[1] != 3 or (ridx is None and R != n) or (ridx is not None and n > 0 and R < 1):
+            raise ValueError(f"dirs must be [n, 3], or [R >= 1, 3] with ridx; got {tuple(dirs.shape)} for {n} samples")
+    elif want_rgb:
+        raise ValueError("the colour needs view directions")
+    L, F = len(sizes), int(feature_dim)
+    if L < 1 or len(planes) != 3 * L:
+        raise ValueError("three planes per level and one size per level")
+    for k, p in enumerate(planes):
+        r = int(sizes[k // 3])
+        if p.dtype != torch.float32:
+            raise RuntimeError(f"nerf_triplane_query: plane {k} is {p.dtype}; this build reads f32 planes")
+        if r < 1 or p.numel() != F * r * r or tuple(p.shape[-3:]) != (F, r, r):
+            raise ValueError(f"plane {k} must be [{F}, {r}, {r}], got {tuple(p.shape)}")
+    want = int(lib.wisp_nerf_mlp_param_count(in_dim, hidden, 4))
+    if params.numel() != want:
+        raise ValueError(f"packed decoder parameters: expected {want} floats for in_dim={in_dim}, got {params.numel()}")
+    parr, pptr = _ptr_array(planes)
+    sarr, sptr = _host_i32(sizes)
+    dev = coords.device
+    rows = n + 2 * pad_rows
+    rgb = torch.empty(rows, 3, dtype=torch.float32, device=dev) if want_rgb else None
+    density = torch.empty(rows, dtype=torch.float32, device=dev)
+    feats = torch.empty(rows, in_dim, dtype=torch.float32, device=dev) if want_feats else None
+    if pad_rows:
+        for t in (rgb, density, feats):
+            if t is not None:
+                t.fill_(float("nan"))
+    with _timed("nerf_triplane_query", n):
+        _check(lib.wisp_nerf_triplane_query(_p(coords), _p(dirs), _p(ridx), R, n, pptr, sptr, L, F, int(bool(sum_lods)), _p(params),
+                                            _DTYPE_CODE.get(params.dtype, -1), in_dim, hidden,
+                                            _p(rgb[pad_rows:] if rgb is not None else None), _p(density[pad_rows:]),
+                                            _p(feats[pad_rows:] if feats is not None else None), _stream()), "nerf_triplane_query")
+    return (rgb, density, feats) if want_feats else (rgb, density)
 
 
 def nerf_mlp_dir_code(ray_dirs, view_freqs=4):

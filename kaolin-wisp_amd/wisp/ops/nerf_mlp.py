@@ -286,6 +286,89 @@ def fused_nerf_octree_query(nef, coords, ray_d=None, ray_dirs=None, ridx=None, l
     return rgb, density.reshape(-1, 1)
 
 
+def _triplane_planes(grid, num):
+    return [p for i in range(num) for p in (grid.features[i].fmx, grid.features[i].fmy, grid.features[i].fmz)]
+
+
+def nerf_triplane_query_supported(nef, lod_idx=None):
+    """The fused inference query of a triplanar field (csrc/nerf_triplane_query.hip) covers this field: a CUDA TriplanarGrid with
+    'linear' interpolation; 'sum' at any valid lod_idx (levels 0..lod_idx), or 'cat' at the last one; f32 contiguous planes; at
+    most 32 feature columns; and the decoder conditions of nerf_query_supported.  WISP_NERF_TRIPLANE_QUERY_FUSED=0 switches it off:
+    the default is on, because on the nerf_triplanar.yaml field the slowest fused repetition beat the fastest modular one in every
+    measured row (profiles/bench_nerf_triplanar_eval.json, fused against modular, median ms: query at 2^18 samples 0.348 against
+    0.375 - slowest fused 0.3669, fastest modular 0.3671: a tie at that size - at 2^21 1.440 against 2.445, an 800 x 800 view at
+    render_batch 10 000 213 against 388 and at 2^17 192 against 371)."""
+    import os
+    from wisp.models.grids import TriplanarGrid
+    if os.environ.get("WISP_NERF_TRIPLANE_QUERY_FUSED", _TRIPLANE_QUERY_DEFAULT) == "0" or not getattr(nef, 'fused_decoder', False) \
+            or torch.is_autocast_enabled():
+        return False
+    grid = nef.grid
+    if not isinstance(grid, TriplanarGrid) or grid.interpolation_type != 'linear' or grid.multiscale_type not in ('cat', 'sum') \
+            or not 1 <= grid.num_lods <= 16 or len(grid.features) != grid.num_lods or grid.feature_dim < 3 or grid.feature_dim % 3:
+        return False
+    last = grid.num_lods - 1
+    if lod_idx is None:
+        lod_idx = last
+    if not 0 <= lod_idx <= last or (grid.multiscale_type == 'cat' and lod_idx != last):
+        return False
+    fdim = grid.feature_dim // 3
+    for i, p in enumerate(_triplane_planes(grid, lod_idx + 1)):
+        size = grid.features[i // 3].fsize + 1
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or tuple(p.shape[-3:]) != (fdim, size, size) \
+                or p.numel() != fdim * size * size:
+            return False
+    if nef.hidden_dim != SUPPORTED["hidden"] or _compute_bf16(nef) or nef.effective_feature_dim() > SUPPORTED["max_in_dim"] \
+            or nef.effective_feature_dim() != (1 if grid.multiscale_type == 'sum' else grid.num_lods) * grid.feature_dim:
+        return False
+    from types import SimpleNamespace
+    if not supports(nef, SimpleNamespace(is_cuda=True, shape=(0, nef.effective_feature_dim()), dtype=torch.float32)):
+        return False                                       # (what the lookup would hand the decoder: fp32 rows on the grid's device)
+    return not any(t is not None and (not t.is_cuda or t.dtype != torch.float32) for t in _decoder_tensors(nef))
+
+
+# the default of WISP_NERF_TRIPLANE_QUERY_FUSED (see nerf_triplane_query_supported)
+_TRIPLANE_QUERY_DEFAULT = "1"
+
+
+def fused_nerf_triplane_query(nef, coords, ray_d=None, ray_dirs=None, ridx=None, lod_idx=None, want_rgb=True, pad_rows=0,
+                              want_feats=False):
+    """(rgb [n,3] fp32 or None, density [n,1] fp32) of NeuralRadianceField.rgba for a field nerf_triplane_query_supported() accepts,
+    in one launch and without a feature tensor: the feature rows of the triplanar SDF kernels' encoder (equal to
+    grid.interpolate's up to the rounding of its contracted multiply-adds) and, on those rows, the bits of fused_nerf_decoder.
+    With want_feats a third result: those rows, fp32 [n, in_dim].  Nothing is cached: the planes are read through their parameters
+    at every call.  View directions as fused_nerf_query takes them.  Inference only: inputs that require a gradient are refused."""
+    grid = nef.grid
+    tensors = [coords, ray_d, ray_dirs] + _triplane_planes(grid, len(grid.features)) + _decoder_tensors(nef)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError("fused_nerf_triplane_query has no backward: call it under torch.no_grad(), or take the modular path")
+    if (ray_d is None) == (ray_dirs is None) and want_rgb:
+        raise ValueError("give the view direction either per sample (ray_d) or per ray (ray_dirs + ridx)")
+    if (ray_dirs is None) != (ridx is None):
+        raise ValueError("ray_dirs and ridx go together")
+    C = _hip()
+    C._need(coords, torch.float32, "coords")               # a field or positions on the CPU: no fallback
+    C._need(grid.features[0].fmx, None, "planes")
+    if lod_idx is None:
+        lod_idx = grid.num_lods - 1
+    sum_lods = grid.multiscale_type == 'sum'
+    if not 0 <= lod_idx < grid.num_lods or (not sum_lods and lod_idx != grid.num_lods - 1):
+        raise ValueError(f"lod_idx {lod_idx}: 'sum' takes any level of the grid, 'cat' the last one")
+    params = _decoder_tensors(nef)
+    H, I = nef.hidden_dim, nef.effective_feature_dim()
+    shapes = ((H, I), (H,), (16, H), (16,), (H, 42), (H,), (H, H), (H,), (3, H), (3,))
+    flat = _flat_view([p.detach() if p is not None else None for p in params])
+    packed = flat if flat is not None else _pack(params, shapes)
+    num = lod_idx + 1
+    planes = [p.detach() for p in _triplane_planes(grid, num)]
+    sizes = [int(grid.features[i].fsize) + 1 for i in range(num)]
+    out = C.nerf_triplane_query(coords.detach(), (ray_d if ray_d is not None else ray_dirs), ridx, planes, sizes, grid.feature_dim // 3,
+                                sum_lods, packed, I, H, want_rgb=want_rgb, pad_rows=pad_rows, want_feats=want_feats)
+    if want_feats:
+        return out[0], out[1].reshape(-1, 1), out[2]
+    return out[0], out[1].reshape(-1, 1)
+
+
 def fused_nerf_decoder(nef, feats, ray_d):
     """(rgb [S,3] fp32, density [S,1] fp32) for the decoder shapes of the reference's app/nerf configs (see SUPPORTED)."""
     compute_bf16 = _compute_bf16(nef)

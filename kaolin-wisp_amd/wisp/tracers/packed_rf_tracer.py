@@ -57,7 +57,8 @@ class PackedRFTracer(BaseTracer):
         """The one-launch field query this call takes, or None: the plain attribute `fused_query` is set (absent = off; not a
         constructor argument, the schema is the reference's), gradients are disabled, no extra channel is asked for and the field
         is one wisp.ops.nerf_mlp.nerf_query_supported accepts (the hash route) or, failing that, one
-        nerf_octree_query_supported accepts (the octree route: OctreeGrid and CodebookOctreeGrid fields)."""
+        nerf_octree_query_supported accepts (the octree route: OctreeGrid and CodebookOctreeGrid fields) or, failing that, one
+        nerf_triplane_query_supported accepts (the triplanar route)."""
         if not getattr(self, 'fused_query', False) or torch.is_grad_enabled() or extra_channels:
             return None
         import wisp.ops.nerf_mlp as ops
@@ -65,6 +66,8 @@ class PackedRFTracer(BaseTracer):
             return ops.fused_nerf_query
         if ops.nerf_octree_query_supported(nef, lod_idx):
             return ops.fused_nerf_octree_query
+        if ops.nerf_triplane_query_supported(nef, lod_idx):
+            return ops.fused_nerf_triplane_query
         return None
 
     def trace(self, nef, rays, channels, extra_channels,
@@ -84,8 +87,9 @@ class PackedRFTracer(BaseTracer):
         fused_query = self._fused_query(nef, lod_idx, extra_channels)
         if fused_query is not None:
             # inference on a shipped NeRF shape: lookup + decoder as ONE launch that reads every sample's direction through its
-            # ray index (csrc/nerf_query.hip for hash grids, csrc/nerf_octree_query.hip for octree and codebook grids) - no
-            # per-sample direction tensor, no feature tensor; same bits as the calls below
+            # ray index (csrc/nerf_query.hip for hash grids, csrc/nerf_octree_query.hip for octree and codebook grids,
+            # csrc/nerf_triplane_query.hip for triplanar grids) - no per-sample direction tensor, no feature tensor; same bits as
+            # the calls below (triplanar: the lookup to rounding, see nerf_triplane_query_supported)
             hit_ray_d = None
             color, density = fused_query(nef, samples, ray_dirs=rays.dirs, ridx=ridx, lod_idx=lod_idx)
         else:

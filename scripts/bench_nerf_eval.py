@@ -15,7 +15,13 @@ field (scripts/render_nerf.py: build_octree_pipeline - level-8 octree of the sce
 'voxel' march with 16 steps; tables and logits drawn at std 0.1), against WISP_NERF_OCTREE_QUERY_FUSED=0.  The query positions are
 the 'voxel' march's own samples of the measured view (16 consecutive samples share a cell), not uniform draws, which would fall
 into empty space.  Each row carries the median, the minimum and the maximum of its repetitions; `fused_max_below_modular_min` is
-the claim the row is read for.  Written to profiles/bench_nerf_octree_eval.json."""
+the claim the row is read for.  Written to profiles/bench_nerf_octree_eval.json.
+
+--grid triplanar: the same plan on the nerf_triplanar.yaml field (scripts/render_nerf.py: build_triplanar_pipeline - planes of 33^2
+to 257^2 texels, 4 features each, 'sum', 'voxel' march of the AABB with 512 steps; planes drawn at std 0.1) and the query of
+csrc/nerf_triplane_query.hip, against WISP_NERF_TRIPLANE_QUERY_FUSED=0 - the modular ops: index_select of the directions, one
+wisp_triplane_fwd launch, the decoder.  The two lookups agree to rounding, not to bits: every row carries the largest colour
+difference.  Written to profiles/bench_nerf_triplanar_eval.json."""
 import argparse
 import json
 import logging
@@ -128,18 +134,93 @@ def octree_main(args):
     return rec
 
 
+def triplanar_main(args):
+    """--grid triplanar: the plan of octree_main on the triplanar field's query"""
+    from render_nerf import build_triplanar_pipeline, orbit_cameras
+    from wisp.ops.nerf_mlp import fused_nerf_triplane_query, nerf_triplane_query_supported
+    from wisp.ops.raygen import generate_centered_pixel_coords, generate_pinhole_rays
+    from wisp.trainers.validation import render
+    dev = "cuda:0"
+    switch = "WISP_NERF_TRIPLANE_QUERY_FUSED"
+    out_path = args.out or os.path.join(ROOT, "profiles", "bench_nerf_triplanar_eval.json")
+    torch.manual_seed(0)
+    pipeline = build_triplanar_pipeline(dev, args.num_steps)
+    nef = pipeline.nef
+    with torch.no_grad():
+        for p in nef.grid.parameters():
+            p.normal_(0.0, 0.1)
+    pipeline.eval()
+    os.environ[switch] = "1"
+    with torch.no_grad():
+        assert nerf_triplane_query_supported(nef)
+    cam = orbit_cameras(1, args.res, args.res)[0]
+    rays = generate_pinhole_rays(cam, generate_centered_pixel_coords(args.res, args.res, device=dev)).reshape(-1, 3)
+    # the query rows take their positions from the tracer's own 'voxel' march of the AABB: a band of rows through the image centre
+    # (the whole view's samples would be hundreds of millions)
+    band = rays[(args.res // 2) * args.res:][:max(1, -(-(1 << 21) // args.num_steps) * 2)]
+    with torch.no_grad():
+        rm = nef.grid.raymarch(band, level=nef.grid.active_lods[-1], num_samples=pipeline.tracer.num_steps, raymarch_type='voxel')
+    total = int(rm.samples.shape[0])
+    assert total > 0
+    sizes = [int(v.fsize) + 1 for v in nef.grid.features]
+    rec = dict(bench="nerf_triplanar_eval", grid=args.grid, device=torch.cuda.get_device_name(0), reps=args.reps,
+               num_steps=args.num_steps, plane_sizes=sizes, band_samples=total, query={}, view={})
+    for log2n in (18, 21):
+        n = 1 << log2n
+        pick = torch.arange(n, device=dev) % total                                  # the march's samples in order, repeated if short
+        coords = rm.samples.index_select(0, pick).contiguous()
+        dirs = band.dirs.index_select(0, rm.ridx.long().index_select(0, pick)).contiguous()
+
+        def fused():
+            with torch.no_grad():
+                fused_nerf_triplane_query(nef, coords, ray_d=dirs)
+
+        def modular():
+            with torch.no_grad():
+                nef(coords=coords, ray_d=dirs, channels=["rgb", "density"])
+        with torch.no_grad():
+            a = fused_nerf_triplane_query(nef, coords, ray_d=dirs)
+            b = nef(coords=coords, ray_d=dirs, channels=["rgb", "density"])
+        row = compare(dict(fused=fused, modular=modular), args.reps)
+        row["equal_bits"] = bool(torch.equal(a[0], b[0]) and torch.equal(a[1].reshape(-1), b[1].reshape(-1)))
+        row["max_abs_diff_rgb"] = float((a[0] - b[0]).abs().max())
+        rec["query"][f"2^{log2n}"] = row
+    for batch in (10000, 1 << 17):
+        out = {}
+
+        def view(flag, key):
+            os.environ[switch] = "1" if flag else "0"
+            torch.manual_seed(1)
+            out[key] = render(pipeline, rays, render_batch=batch, channels=["rgb"], fused_query=True).rgb
+        row = compare(dict(fused=lambda: view(True, "f"), modular=lambda: view(False, "m")), args.reps)
+        os.environ[switch] = "1"
+        row["equal_bits"] = bool(torch.equal(out["f"], out["m"]))
+        row["max_abs_diff_rgb"] = float((out["f"] - out["m"]).abs().max())
+        rec["view"][f"render_batch_{batch}"] = dict(res=args.res, reps=args.reps, **row)
+    line = json.dumps(rec)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    print(line)
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--res", type=int, default=800)
     ap.add_argument("--num-steps", type=int, default=512)
     ap.add_argument("--out", default=None, help="default: profiles/bench_nerf_eval.json, or profiles/bench_nerf_octree_eval.json "
-                                                "(one line per grid) with --grid octree / codebook")
-    ap.add_argument("--grid", choices=("hash", "octree", "codebook"), default="hash")
+                                                "(one line per grid) with --grid octree / codebook, or "
+                                                "profiles/bench_nerf_triplanar_eval.json with --grid triplanar")
+    ap.add_argument("--grid", choices=("hash", "octree", "codebook", "triplanar"), default="hash")
     ap.add_argument("--octree-level", type=int, default=8, help="--grid octree / codebook: depth of the scene's octree")
     ap.add_argument("--cloud-rays", type=int, default=1 << 21, help="--grid octree / codebook: rays of the surface point cloud")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.WARNING)
+    if args.grid == "triplanar":
+        return triplanar_main(args)
     if args.grid != "hash":
         return octree_main(args)
     if args.out is None:
